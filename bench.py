@@ -15,9 +15,12 @@ weights).  ``value`` = total rows processed per second over all ranks.
     torchrun --nproc-per-node 8 bench.py --gpus 8 ...
     python bench.py --model gbdt    # GBDT rounds/sec (500 trees depth 7, 256 bins) config alone
 
-The default line carries both halves of the metric: ``value`` = MLP rows/s, and after the MLP
-rows are freed the same process times ``--gbdt-steps`` boosting rounds on 100M x 1000 uint8 codes
-per GPU (``gbdt_rounds_per_s`` / ``gbdt_ms_per_round``; ``--gbdt-steps 0`` skips it).
+A plain run sets up, warms up, times ``--steps`` MLP steps and prints the line (``value`` = MLP
+rows/s, ``ms_per_step`` = milliseconds per timed step); ``--dump-outputs DIR`` also writes what the
+timed steps computed as ``DIR/<name>.npy``.  With ``--full`` the line carries both halves of the
+metric: after the MLP rows are freed the same process times ``--gbdt-steps`` boosting rounds on
+100M x 1000 uint8 codes per GPU (``gbdt_rounds_per_s`` / ``gbdt_ms_per_round``; ``--gbdt-steps 0``
+skips it).
     python bench.py --model varsel  # 10k-feature MLP + SE varselect config (sparse planted rule, recall@20)
     python bench.py --model lr      # LR 100k-row CSV local (CPU plumbing) config
     python bench.py --model stats   # stats (K4 exact cuts + histograms) 100M x 1000 per GPU
@@ -148,6 +151,18 @@ def make_synthetic(rows, n_in, k0, device, seed, sparse_k=0):
     return x, y
 
 
+def dump_mlp_outputs(path, tr, errs):
+    """``--dump-outputs``: what the timed steps handed their caller, as ``<name>.npy``: the
+    training error every timed step returned (float64), and the state the last step left in the
+    trainer - its all-reduced fp32 gradient and the fp32 weights after the RPROP update (flat
+    buffers, per-layer [out, in_pad] blocks in layer order; 2.4 MB each for 1000-500-200-1).  Data and
+    initial weights are seeded, so two builds run with the same arguments compare file for file."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "train_errors.npy"), np.asarray(errs, dtype=np.float64))
+    np.save(os.path.join(path, "gradient.npy"), tr.grad.detach().float().cpu().numpy())
+    np.save(os.path.join(path, "weights.npy"), tr.params.flat.detach().float().cpu().numpy())
+
+
 def bench_mlp(a, dev, info):
     from shifu_amd.models.nn import MLPSpec, MLPTrainer, TrainData
     from shifu_amd.parallel import dist
@@ -191,6 +206,8 @@ def bench_mlp(a, dev, info):
         comm_ms = sum(e1 - e0 for e0, e1 in tr.comm_events) * 1e3
     tr.comm_events = None
     log(f"[bench] train errors {['%.6f' % e for e in errs]}")
+    if a.dump_outputs and info.rank == 0:
+        dump_mlp_outputs(a.dump_outputs, tr, errs)
     flops_row = 2 * (a.cols * 500 + 500 * 200 + 200) * 2 + 2 * 500 * 200   # fwd+wgrad all, dgrad layer2
     return dt, errs, flops_row, {"t_local": t_local, "comm_ms": comm_ms}
 
@@ -941,7 +958,13 @@ def main():
     ap.add_argument("--propagation", default="R")
     ap.add_argument("--gbdt-rows", type=int, default=None,
                     help="rows per GPU of the GBDT half of the default line (default 100M on GPU)")
-    ap.add_argument("--gbdt-steps", type=int, default=5, help="timed boosting rounds (0 = MLP only)")
+    ap.add_argument("--full", action="store_true",
+                    help="default (MLP) line: also time the GBDT half of the metric after the MLP steps "
+                         "(gbdt_* keys); a plain run times the MLP steps alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="default (MLP) line: after the timed steps write what they computed (per-step training "
+                         "errors, last gradient, final weights) as DIR/<name>.npy")
+    ap.add_argument("--gbdt-steps", type=int, default=5, help="--full: timed boosting rounds (0 = MLP only)")
     ap.add_argument("--gbdt-warmup", type=int, default=1)
     ap.add_argument("--gbdt-data", default="both", choices=["both", "favourable", "balanced"],
                     help="GBDT labels: favourable (rule on two features: small non-root nodes), balanced (dense "
@@ -964,6 +987,10 @@ def main():
     ap.add_argument("--pipeline-epochs", type=int, default=40,
                     help="pipeline: numTrainEpochs of the NN (varsel SE trains half of them)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.model != "mlp":
+        ap.error("--dump-outputs is implemented for the default (MLP) benchmark only")
 
     from shifu_amd.parallel import dist
     info = dist.init_from_env()
@@ -1044,7 +1071,7 @@ def main():
         if gpu:      # HBM headroom per rank (RCCL buffers for N > 1 must fit beside the rows)
             out["hbm_peak_gb"] = torch.cuda.max_memory_allocated(dev) / 1e9
             out["hbm_total_gb"] = torch.cuda.get_device_properties(dev).total_memory / 1e9
-        if a.gbdt_steps > 0:
+        if a.full and a.gbdt_steps > 0:
             out.update(gbdt_half(a, dev, info))
     if info.rank == 0:
         print(json.dumps(out), flush=True)

@@ -19,7 +19,7 @@ def _run(args, timeout=600):
 
 
 def test_bench_gpus2_launches_two_ranks():
-    out = _run(["--gpus", "2", "--rows", "4000", "--cols", "64", "--steps", "2", "--warmup", "1",
+    out = _run(["--gpus", "2", "--rows", "4000", "--cols", "64", "--steps", "2", "--warmup", "1", "--full",
                 "--gbdt-steps", "1", "--gbdt-warmup", "0", "--gbdt-rows", "500"])
     assert out["n_gpus"] == 2
     assert out["config"]["parallelism"] == "dp2"
@@ -34,6 +34,29 @@ def test_bench_gpus1_single_process():
     out = _run(["--gpus", "1", "--rows", "2000", "--cols", "64", "--steps", "1", "--warmup", "0",
                 "--gbdt-steps", "0"])
     assert out["n_gpus"] == 1 and out["config"]["parallelism"] == "dp1"
+
+
+def test_bench_plain_run_is_mlp_only_and_dumps_reproducible_outputs(tmp_path):
+    """A plain run times the MLP steps alone (the GBDT half needs --full); --dump-outputs writes what
+    the timed steps computed, from the same seeded data and weights in every run.  The CPU path sums
+    in fp32 over threads in no fixed order, so runs agree to fp32 summation error (2000 rows: well
+    inside 1e-4 of the largest gradient entry), not bit for bit; RPROP steps by the gradient's sign,
+    so the weights are only checked for shape."""
+    import numpy as np
+    dirs = [str(tmp_path / d) for d in ("a", "b")]
+    for d in dirs:
+        out = _run(["--gpus", "1", "--rows", "2000", "--cols", "64", "--steps", "3", "--warmup", "1",
+                    "--dump-outputs", d])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0
+        assert not [k for k in out if k.startswith("gbdt")]
+    assert sorted(os.listdir(dirs[0])) == ["gradient.npy", "train_errors.npy", "weights.npy"]
+    for f in os.listdir(dirs[0]):
+        a, b = np.load(os.path.join(dirs[0], f)), np.load(os.path.join(dirs[1], f))
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all() and a.shape == b.shape
+        if f != "weights.npy":
+            np.testing.assert_allclose(a, b, rtol=0, atol=1e-4 * np.abs(a).max())
+    errs = np.load(os.path.join(dirs[0], "train_errors.npy"))
+    assert errs.shape == (3,) and errs[-1] == out["final_train_error"]
 
 
 def test_bench_launcher_fails_fast_when_a_rank_dies():

@@ -5,7 +5,6 @@ import os
 import numpy as np
 import pytest
 
-from conftest import REF_TR
 from shifu_amd.config import jsonio
 from shifu_amd.config.column_config import load_column_configs, save_column_configs
 from shifu_amd.config.model_config import ModelConfig, create_init_model_config
@@ -109,7 +108,7 @@ def test_readable_zip_spec_matches_reference_bytes(tmp_path, ref_resources):
     import json
     import zipfile
     from shifu_amd.steps.misc import gbt_to_zip, zip_to_gbt
-    spec = os.path.join(REF_TR, "example", "readablespec")
+    spec = os.path.join(ref_resources, "example", "readablespec")
     zip_to_gbt(os.path.join(spec, "model0.zip"), str(tmp_path / "m.gbt"))
     ours = gzip.decompress(open(tmp_path / "m.gbt", "rb").read())
     assert ours == gzip.decompress(open(os.path.join(spec, "model1.gbt"), "rb").read())
@@ -126,7 +125,7 @@ def test_legacy_pre_versioned_gbt_fixture(ref_resources):
     follow from the stored tree (root worst_concave_points < 0.14781, ...)."""
     import numpy as np
     from shifu_amd.formats.tree_format import read_tree_model, CONTINUOUS
-    path = os.path.join(REF_TR, "example", "wdbc", "wdbcModelSetLocal", "models", "model0.gbt")
+    path = os.path.join(ref_resources, "example", "wdbc", "wdbcModelSetLocal", "models", "model0.gbt")
     m = read_tree_model(path)
     assert m.algorithm == "GBT" and m.loss == "squared" and m.version == 0
     t = m.bags[0][0]

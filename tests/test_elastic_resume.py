@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 import torch.multiprocessing as mp
 
-from tests.test_synthetic_models import _mc, _run
+# _cpu (autouse): the in-process runs stay on the CPU like the ranks and subprocesses they are compared with
+from tests.test_synthetic_models import _cpu, _mc, _run  # noqa: F401
 
 
 def _port():

@@ -8,7 +8,8 @@ import pytest
 import torch.multiprocessing as mp
 
 from tests.test_elastic_resume import _port
-from tests.test_synthetic_models import _mc, _run
+# _cpu (autouse): the single-process run stays on the CPU like the ranks it is compared with
+from tests.test_synthetic_models import _cpu, _mc, _run  # noqa: F401
 
 
 def _rank_train(rank, world, port, root):

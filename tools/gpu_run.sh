@@ -4,7 +4,7 @@
 #   tests            full `pytest -m gpu` suite
 #   tests:<k-expr>   GPU tests matching a -k expression ("=" stands for a space: tests:a=or=b)
 #   smoke            __graft_entry__.smoke()
-#   bench            default bench line (MLP + GBDT halves)
+#   bench            default bench line (MLP steps alone; bench:--full adds the GBDT half)
 #   bench:<args>     bench.py with extra args, e.g. bench:--model=gbdt (use '=' not spaces)
 #   prof:<args>      rocprofv3 --kernel-trace --stats around bench.py <args>
 #   pmc:<ctrs>:<args> rocprofv3 --pmc <ctrs> (comma list) around bench.py <args>
