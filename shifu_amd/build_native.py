@@ -24,6 +24,10 @@ RT_SRC = ROOT / "runtime" / "csrc"
 LIB_DIR = ROOT / "ops" / "_lib"
 OBJ_DIR = LIB_DIR / "obj"
 ARCH = os.environ.get("SHIFU_OFFLOAD_ARCH", "gfx950")
+# per-source extra hipcc flags.  New kernels are compiled without the packed-fp32 VALU forms
+# (v_pk_*_f32); the older sources keep the flags their measurements were taken with
+NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"gbdt_wide_kernels.hip": NO_PK_F32}
 
 
 def _hipcc() -> str:
@@ -60,7 +64,7 @@ def build_hip(force=False, jobs=8, verbose=False) -> Path:
         o = OBJ_DIR / (s.stem + ".hip.o")
         objs.append(o)
         if force or _newer(o, [s, *hdrs]):
-            todo.append([hipcc, *flags, "-c", str(s), "-o", str(o)])
+            todo.append([hipcc, *flags, *EXTRA_FLAGS.get(s.name, []), "-c", str(s), "-o", str(o)])
     if todo:
         with ThreadPoolExecutor(max(1, jobs)) as ex:
             for r in ex.map(_run, todo):

@@ -495,7 +495,9 @@ def record_to_heap_tree(rec: TreeRecord, columns, min_depth: int = 1):
     def max_id(nd):
         return 0 if nd is None else max(nd.id, max_id(nd.left), max_id(nd.right))
     depth = max(min_depth, int(max_id(rec.root)).bit_length())
-    t = Tree(depth, float(rec.learning_rate))
+    # left-set words: 8 (256 bins), or what the widest categorical column's categories + missing need
+    ncat_max = max((len(c.bin_category or []) + 1 for c in columns if c.is_categorical()), default=0)
+    t = Tree(depth, float(rec.learning_rate), max(8, (ncat_max + 31) // 32))
     used = set()
 
     def put(nd):

@@ -36,7 +36,9 @@ from ..utils.trace import trace_range
 
 _log = get_logger("models.gbdt")
 
-NB = 256
+NB = 256                    # bins of a narrow feature (uint8 codes)
+WIDE_MAX = 16384            # most bins of a wide feature (gbdt_wide_kernels.hip WMAX)
+WIDE_PAD = 1024             # a wide feature's bins are padded to the wide kernels' block size (WT)
 FG = 32                     # features per histogram work-item group (gbdt_kernels.hip FG)
 QF = 128                    # features per 128-B row record of the quad-blocked bins (QF)
 IMPURITY_IDS = {"variance": 0, "friedmanmse": 1, "entropy": 2, "gini": 3}
@@ -130,13 +132,14 @@ class TreeConfig:
 class Tree:
     """Heap-indexed tree (node id 1 = root, children 2i / 2i+1 as ``Node.leftIndex``)."""
 
-    def __init__(self, max_depth: int, weight: float = 1.0):
+    def __init__(self, max_depth: int, weight: float = 1.0, cat_words: int = 8):
         self.max_depth = max_depth
         self.max_nodes = 1 << max_depth
         m = self.max_nodes
         self.feat = np.full(m, -1, dtype=np.int32)      # feature index (into the binned matrix)
         self.thr = np.full(m, -1, dtype=np.int32)       # numeric: left iff bin <= thr
-        self.cat_left = np.zeros((m, 8), dtype=np.uint32)
+        # categorical left sets, 32 bins per word: 8 words unless the data has wide features
+        self.cat_left = np.zeros((m, cat_words), dtype=np.uint32)
         self.value = np.zeros(m, dtype=np.float32)
         self.class_value = np.zeros(m, dtype=np.float32)  # multi-class RF: argmax class per node
         self.classification = False
@@ -169,7 +172,8 @@ class Tree:
             fa = np.where(active, f, 0)
             b = bins[np.arange(n), fa].astype(np.int64)
             catm = is_cat[fa].astype(bool)
-            bit = (self.cat_left[ids, b >> 5] >> (b & 31).astype(np.uint32)) & 1
+            wd = np.minimum(b >> 5, self.cat_left.shape[1] - 1)     # (a numeric code may exceed the set width)
+            bit = (self.cat_left[ids, wd] >> (b & 31).astype(np.uint32)) & 1
             left = np.where(catm, bit == 1, b <= self.thr[ids])
             ids = np.where(active, np.where(left, 2 * ids, 2 * ids + 1), ids)
         return (self.class_value if classes else self.value)[ids]
@@ -191,6 +195,32 @@ class BinnedData:
     # out-of-core: bins in pinned host memory, read by the kernels in place over the
     # host link (the device address of the mapping); targets / weights / predictions stay in HBM
     bins_dptr: int | None = None
+    # wide features (257 .. WIDE_MAX bins): uint16 codes, column-major [Fw][N] in ascending feature
+    # index, always in HBM (2 B x N x Fw); their byte in ``bins`` is 0
+    wbins: torch.Tensor | None = None
+
+    def __post_init__(self):
+        self.wide_feats = _wide_feats(self.nbins)
+        # feature -> its column of wbins, -1: narrow
+        self.wide_of = np.full(len(self.nbins), -1, np.int32)
+        self.wide_of[self.wide_feats] = np.arange(len(self.wide_feats), dtype=np.int32)
+        if len(self.wide_feats) and (self.wbins is None or self.wbins.shape[0] != len(self.wide_feats)):
+            raise ValueError("features with more than 256 bins need their uint16 columns: build the data "
+                             "with BinnedData.from_codes / host_resident")
+
+    @property
+    def n_wide(self) -> int:
+        return len(self.wide_feats)
+
+    @property
+    def nbins_narrow(self) -> np.ndarray:
+        """``nbins`` as the narrow kernels see it: 1 for a wide feature (no split candidate)."""
+        return np.where(self.nbins > NB, 1, self.nbins).astype(np.int32)
+
+    @property
+    def cat_words(self) -> int:
+        """32-bit words of a categorical left set: 8, or enough for the widest feature."""
+        return 8 if not self.n_wide else int((int(self.nbins.max()) + 31) // 32)
 
     @property
     def n(self):
@@ -214,7 +244,11 @@ class BinnedData:
     def codes(self) -> torch.Tensor:
         """Row-major ``[N, F]`` view (a copy) of the codes - CPU paths and tests."""
         q, n, _ = self.bins.shape
-        return self.bins.permute(1, 0, 2).reshape(n, q * QF)[:, : self.n_feat]
+        c = self.bins.permute(1, 0, 2).reshape(n, q * QF)[:, : self.n_feat]
+        if self.n_wide:          # the true codes: int16 with the wide columns laid over their zero bytes
+            c = c.to(torch.int16)
+            c[:, torch.from_numpy(self.wide_feats).long()] = self.wbins.view(torch.int16).t().to(c.device)
+        return c
 
     @staticmethod
     def host_resident(codes, y, nbins, is_cat=None, sig=None, device="cuda", rows=None):
@@ -224,21 +258,25 @@ class BinnedData:
         n, f = codes.shape
         if rows is not None:
             n = len(rows)
+        wide = _wide_feats(nbins)
         b = torch.empty((f + QF - 1) // QF, n, QF, dtype=torch.uint8, pin_memory=True)
-        BinnedData.blocked(codes, "cpu", rows, out=b)
+        BinnedData.blocked(codes, "cpu", rows, out=b, wide=wide)
         dptr = _host_device_pointer(b)
         d = BinnedData.from_codes(np.zeros((0, f), np.uint8), np.zeros(0), nbins, is_cat, None, device)
         d.bins, d.bins_dptr = b, dptr
+        if len(wide):
+            d.wbins = BinnedData.wide_columns(codes, wide, device, rows)
         d.y = torch.as_tensor(y, dtype=torch.float32).reshape(n).to(device)
         d.sig = None if sig is None else torch.as_tensor(sig, dtype=torch.float32).reshape(n).to(device)
         return d
 
     @staticmethod
-    def blocked(codes, device="cpu", rows=None, out=None) -> torch.Tensor:
+    def blocked(codes, device="cpu", rows=None, out=None, wide=()) -> torch.Tensor:
         """Row-major codes [N, F] (torch or numpy incl. a uint8 memmap, any int dtype) -> quad-blocked
         uint8 [Q, N', 128] on ``device`` (128 features of a row = one 128-B record), filled one
         32-feature group at a time (optionally only ``rows``): host memory stays at one group
-        slice, never an int32 copy of the whole matrix."""
+        slice, never an int32 copy of the whole matrix.  The bytes of the ``wide`` features (more
+        than 256 bins, see :meth:`wide_columns`) are 0."""
         n, f = codes.shape
         if rows is not None:
             n = len(rows)
@@ -256,7 +294,19 @@ class BinnedData:
                 blk = torch.from_numpy(blk)
             o = (gi % (QF // FG)) * FG
             b[gi // (QF // FG), :, o: o + c1 - c0] = blk.to(device=device, dtype=torch.uint8)
+        for fw in wide:
+            b[fw // QF, :, fw % QF] = 0
         return b
+
+    @staticmethod
+    def wide_columns(codes, wide, device="cpu", rows=None) -> torch.Tensor:
+        """The ``wide`` features' codes as uint16 ``[Fw, N']`` (column-major) on ``device``."""
+        cols = []
+        for fw in wide:
+            c = codes[:, int(fw)] if rows is None else codes[rows, int(fw)]
+            c = c.cpu().numpy() if isinstance(c, torch.Tensor) else np.asarray(c)
+            cols.append(np.ascontiguousarray(c, dtype=np.uint16))
+        return torch.from_numpy(np.stack(cols)).to(device)
 
     @staticmethod
     def from_codes(codes, y, nbins, is_cat=None, sig=None, device="cpu", rows=None):
@@ -264,12 +314,24 @@ class BinnedData:
             codes = torch.as_tensor(codes)
         f = codes.shape[1]
         n = codes.shape[0] if rows is None else len(rows)
-        b = BinnedData.blocked(codes, device, rows)
+        nb = np.asarray(nbins, dtype=np.int32).reshape(f)
+        wide = _wide_feats(nb)
+        b = BinnedData.blocked(codes, device, rows, wide=wide)
+        wb = BinnedData.wide_columns(codes, wide, device, rows) if len(wide) else None
         y = torch.as_tensor(y, dtype=torch.float32).reshape(n).to(device)
         s = None if sig is None else torch.as_tensor(sig, dtype=torch.float32).reshape(n).to(device)
-        nb = np.asarray(nbins, dtype=np.int32).reshape(f)
         ic = np.zeros(f, np.uint8) if is_cat is None else np.asarray(is_cat, dtype=np.uint8).reshape(f)
-        return BinnedData(b, y, s, nb, ic, f)
+        return BinnedData(b, y, s, nb, ic, f, wbins=wb)
+
+
+def _wide_feats(nbins) -> np.ndarray:
+    """Indices of the features with more than 256 bins (ascending); more than WIDE_MAX is refused."""
+    nb = np.asarray(nbins).reshape(-1)
+    bad = np.flatnonzero(nb > WIDE_MAX)
+    if len(bad):
+        raise ValueError(f"GBT/RF feature {int(bad[0])} has {int(nb[bad[0]])} bins; at most {WIDE_MAX} are "
+                         f"supported")
+    return np.flatnonzero(nb > NB).astype(np.int32)
 
 
 class TreeTrainer:
@@ -290,7 +352,22 @@ class TreeTrainer:
         self.trees: list[Tree] = []
         self.pred = torch.zeros(data.n, dtype=torch.float32, device=self.dev)
         self.vpred = None if valid is None else torch.zeros(valid.n, dtype=torch.float32, device=valid.device)
-        self.nbins_t = _h2d(data.nbins.astype(np.int32), self.dev)
+        self.nbins_t = _h2d(data.nbins_narrow, self.dev)      # wide features: no narrow candidate
+        # wide features (more than 256 bins): own histograms [.., Fw, nbp] and kernels
+        self.Fw = data.n_wide
+        self.CW = data.cat_words
+        if self.Fw:
+            if cfg.is_multiclass:
+                raise ValueError(f"native multi-class RF does not support features with more than {NB} bins "
+                                 f"(feature {int(data.wide_feats[0])} has {int(data.nbins[data.wide_feats[0]])})")
+            if valid is not None and not np.array_equal(valid.nbins, data.nbins):
+                raise ValueError("validation data must have the training data's bin counts")
+            nbw = data.nbins[data.wide_feats].astype(np.int32)
+            self.nbp = _pad_bins(int(nbw.max()))
+            self.nbins_w_t = _h2d(nbw, self.dev)
+            self.wide_feat_t = _h2d(data.wide_feats, self.dev)
+            self.wide_of_t = _h2d(data.wide_of, self.dev)
+        self._hw_prev = None            # previous level's wide histograms (sibling subtraction)
         self.is_cat_t = _h2d(data.is_cat.astype(np.uint8), self.dev)
         self.rng = np.random.default_rng(cfg.seed)
         self.tgen = torch.Generator(device=self.dev).manual_seed(cfg.seed + 17 * dist.info().rank)
@@ -386,7 +463,8 @@ class TreeTrainer:
         # them), so below the root the histogram reads them contiguously and gathers only the bins;
         # at the root positions are rows
         self._wg_pos = (w, gg) if (self.gpu and T == 1 and not c.is_multiclass and WG_POS) else None
-        trees = [Tree(c.max_depth, weight) for _ in range(T)]
+        trees = [Tree(c.max_depth, weight, self.CW) for _ in range(T)]
+        self._hw_prev = None
         rngs = [np.random.default_rng([c.seed, int(t)]) for t in tids]
         pos2row = torch.arange(P, dtype=torch.int32, device=self.dev)
         pos_node = (pos2row // max(1, n)).to(torch.int32) if T > 1 else torch.zeros(n, dtype=torch.int32,
@@ -470,7 +548,7 @@ class TreeTrainer:
             # decisions ------------------------------------------------------------------
             split_feat = np.full(len(nodes), -1, dtype=np.int32)
             split_bin = np.full(len(nodes), -1, dtype=np.int32)
-            cat_left = np.zeros((len(nodes), 8), dtype=np.uint32)
+            cat_left = np.zeros((len(nodes), self.CW), dtype=np.uint32)
             children = []
             last = level + 1 >= c.max_depth
             allowed = None
@@ -498,7 +576,8 @@ class TreeTrainer:
                 tree.gain[nid] = gain
                 tree.features_used.append(f)
                 if d.is_cat[f]:
-                    order = hist["cat_order"][s_][f]
+                    jw = d.wide_of[f]
+                    order = hist["cat_order"][s_][f] if jw < 0 else hist["cat_order_w"][s_][jw]
                     left_bins = order[: int(b) + 1]
                     for lb in left_bins:       # (int: a uint8 shift stays uint8 under NumPy 2)
                         lb = int(lb)
@@ -562,7 +641,7 @@ class TreeTrainer:
     def _pipelined(self, T: int) -> bool:
         """Device decisions + device node ranges for this growth (see _grow_levels_dev)."""
         c = self.cfg
-        return (DEV_DECIDE and self.gpu and not c.is_multiclass and c.max_leaves <= 0
+        return (DEV_DECIDE and self.gpu and not c.is_multiclass and c.max_leaves <= 0 and not self.Fw
                 and T * 2 ** max(0, c.max_depth - 2) <= 512)
 
     def _grow_levels_dev(self, trees, rngs, nodes, pos2row, pos_node, w, gg, level_log, n_leaves):
@@ -854,6 +933,31 @@ class TreeTrainer:
         ni[slot[nd][keep], grp[keep], ch[keep]] = np.arange(len(items), dtype=np.int32)
         return items, ni, max_items
 
+    def _make_wide_items(self, nodes):
+        """Wide-feature work items [n, 4] = (node slot, lo, hi, wide feature j) of the built nodes
+        (exact row ranges: the host-decision loop) and node_items [n_nodes, Fw, max_items] (item
+        ids, -1 padded).  A node's rows are cut into chunks of at least WIDE_MIN_ROWS rows so that
+        about WIDE_TARGET_ITEMS blocks share a level; the int64 sums do not depend on the cut."""
+        Fw = self.Fw
+        bz = [z for z in nodes if z["built"] and z["end"] > z["start"]]
+        rows_built = sum(z["end"] - z["start"] for z in bz)
+        items, per_node = [], []
+        for z in bz:
+            m = z["end"] - z["start"]
+            k = min(64, max(1, m // WIDE_MIN_ROWS), max(1, round(WIDE_TARGET_ITEMS * m / rows_built / Fw)))
+            step = -(-m // k)
+            k = -(-m // step)
+            per_node.append((z["slot"], len(items), k))
+            for j in range(Fw):
+                for ch in range(k):
+                    lo = z["start"] + ch * step
+                    items.append((z["slot"], lo, min(z["end"], lo + step), j))
+        max_items = max([k for _, _, k in per_node], default=1)
+        ni = np.full((len(nodes), Fw, max_items), -1, np.int32)
+        for slot, first, k in per_node:
+            ni[slot, :, :k] = first + np.arange(Fw * k, dtype=np.int32).reshape(Fw, k)
+        return np.asarray(items, np.int32).reshape(-1, 4), ni, max_items
+
     def _hist_allreduce(self, h: torch.Tensor) -> None:
         """All-reduce one level's built-node histograms (one bucket per level), timed: HIP events
         on the GPU (read when the tree is done), host wall time on the CPU (gloo is synchronous)."""
@@ -899,17 +1003,23 @@ class TreeTrainer:
         # so no zero fill of the level's histograms (up to 64 nodes x 4 MB)
         alloc = torch.empty if self.gpu else torch.zeros
         hist = alloc(nn, 2, F, NB, dtype=torch.int64, device=self.dev)
+        wide = None
+        if self.Fw:     # the wide features' histograms, previous level's for the subtraction, orders (out)
+            wide = {"hist": alloc(nn, 2, self.Fw, self.nbp, dtype=torch.int64, device=self.dev),
+                    "prev": self._hw_prev, "cat_order": None}
+            self._hw_prev = wide["hist"]
         if self.gpu and raw:
             cand, cat_order = self._build_and_split_hip(nodes, n_built, g, w, pos2row, hist_prev, hist, mask,
                                                         imp, min_inst, min_gain, rng=rng, raw=True)
             return {"hist": hist, "cand": cand, "cat_order": cat_order}
         if self.gpu:
             best, cat_order = self._build_and_split_hip(nodes, n_built, g, w, pos2row, hist_prev, hist, mask,
-                                                        imp, min_inst, min_gain)
+                                                        imp, min_inst, min_gain, wide=wide)
         else:
             best, cat_order = self._build_and_split_torch(nodes, n_built, g, w, pos2row, hist_prev, hist, mask,
-                                                          imp, min_inst, min_gain)
-        return {"hist": hist, "best": best, "cat_order": cat_order}
+                                                          imp, min_inst, min_gain, wide=wide)
+        return {"hist": hist, "best": best, "cat_order": cat_order,
+                "cat_order_w": None if wide is None else wide["cat_order"]}
 
     def _select_best(self, cand: torch.Tensor, nn: int):
         """cand [nn, F, 8] -> per node best (lowest feature on ties)."""
@@ -928,7 +1038,7 @@ class TreeTrainer:
         return res
 
     def _build_and_split_hip(self, nodes, n_built, g, w, pos2row, hist_prev, hist, mask, imp, min_inst, min_gain,
-                             rng=None, raw=False):
+                             rng=None, raw=False, wide=None):
         from ..ops import _native as nat
         d = self.data
         F, nn = self.F, len(nodes)
@@ -972,6 +1082,28 @@ class TreeTrainer:
                 ls.append({"level": self._level, "nodes_built": int(n_built), "rows": rows, "ev": (ev0, ev1)})
         else:
             slab = torch.zeros(1, 2, FG, NB, dtype=torch.int64, device=self.dev)
+        if wide is not None:        # one block per {node, row range, wide feature}
+            witems, wni, wmax = self._make_wide_items(nodes)
+            wni_t = _h2d(wni, self.dev)
+            if len(witems):
+                wit = _h2d(witems, self.dev)
+                wslab = torch.empty(len(witems), 2, self.nbp, dtype=torch.int64, device=self.dev)
+                p2r = None if self._root_level else pos2row
+                by_pos = p2r is not None and self._wg_pos is not None
+                wv, gv = self._wg_pos if by_pos else (w, g)
+                nat.call_hip("shifu_gbdt_hist_wide", d.wbins, d.n, self.nbins_w_t, p2r, wv, gv, int(by_pos), wit,
+                             len(witems), wslab, self.nbp, self.scale_w, self.scale_g, self._nmod, st)
+            else:
+                wslab = torch.zeros(1, 2, self.nbp, dtype=torch.int64, device=self.dev)
+            cow = None
+            if d.is_cat[d.wide_feats].any():
+                cow = torch.zeros(nn, self.Fw, self.nbp, dtype=torch.int16, device=self.dev)   # uint16 bits
+
+            def split_wide(mode, node_list, n_list, parent=None, par_t=None, sib_t=None):
+                nat.call_hip("shifu_gbdt_split_wide", wslab, wni_t, wmax, parent, par_t, sib_t, wide["hist"],
+                             node_list, n_list, self.wide_feat_t, self.nbins_w_t, self.Fw, self.nbp, self.is_cat_t,
+                             mask if mode else None, cand, cow if mode else None, F, mode, imp, min_inst,
+                             min_gain, 1.0 / self.scale_w, 1.0 / self.scale_g, st)
         built = _h2d(np.asarray([z["slot"] for z in nodes if z["built"]], np.int32), self.dev)
         derived = [z for z in nodes if not z["built"]]
         if n_built:
@@ -979,10 +1111,15 @@ class TreeTrainer:
                          hist.data_ptr(), built.data_ptr(), n_built, feat_list.data_ptr(), F,
                          self.nbins_t.data_ptr(), self.is_cat_t.data_ptr(), None, cand.data_ptr(), None, F, 0, imp,
                          0, min_inst, min_gain, 1.0 / self.scale_w, 1.0 / self.scale_g, st)
+            if wide is not None:
+                split_wide(0, built, n_built)
         self.timings["hist"] += time.perf_counter() - t0
-        # cross-rank reduction of the built-node histograms (one RCCL bucket per level)
+        # cross-rank reduction of the built-node histograms (one RCCL bucket per level, one more
+        # for the wide features' histograms)
         if n_built:
             self._hist_allreduce(hist[:n_built])
+            if wide is not None:
+                self._hist_allreduce(wide["hist"][:n_built])
         mptr = None if mask is None else mask.data_ptr()
         cptr = None if cat_order is None else cat_order.data_ptr()
         if n_built:
@@ -990,6 +1127,8 @@ class TreeTrainer:
                          hist.data_ptr(), built.data_ptr(), n_built, feat_list.data_ptr(), F,
                          self.nbins_t.data_ptr(), self.is_cat_t.data_ptr(), mptr, cand.data_ptr(), cptr, F, 2, imp,
                          1, min_inst, min_gain, 1.0 / self.scale_w, 1.0 / self.scale_g, st)
+            if wide is not None:
+                split_wide(2, built, n_built)
         if derived:
             dl = _h2d(np.asarray([z["slot"] for z in derived], np.int32), self.dev)
             par = np.zeros(nn, np.int32)
@@ -1004,9 +1143,13 @@ class TreeTrainer:
                          feat_list.data_ptr(), F, self.nbins_t.data_ptr(), self.is_cat_t.data_ptr(), mptr,
                          cand.data_ptr(), cptr, F, 1, imp, 1, min_inst, min_gain, 1.0 / self.scale_w,
                          1.0 / self.scale_g, st)
+            if wide is not None:
+                split_wide(1, dl, len(derived), wide["prev"], par_t, sib_t)
         if raw:
             return cand, cat_order
         best = self._select_best(cand, nn)
+        if wide is not None and cow is not None:
+            wide["cat_order"] = cow.cpu().numpy().view(np.uint16)
         co = None if cat_order is None else cat_order.cpu().numpy()
         return best, co
 
@@ -1198,11 +1341,16 @@ class TreeTrainer:
         return {"hist": hists, "best": best, "cat_order": cat_order, "class_lr": class_lr}
 
     def _build_and_split_torch(self, nodes, n_built, g, w, pos2row, hist_prev, hist, mask, imp, min_inst,
-                               min_gain):
-        """CPU oracle: same decomposition with torch ops (fp64 scan)."""
+                               min_gain, wide=None):
+        """CPU oracle: same decomposition with torch ops (fp64 scan; wide features: int64 prefix)."""
         d = self.data
         F, nn = self.F, len(nodes)
         bins = self._codes().long()
+        if wide is not None:        # the narrow histograms see what the uint8 array holds: 0
+            wf = torch.from_numpy(d.wide_feats).long()
+            wcodes = bins[:, wf]
+            bins = bins.clone()
+            bins[:, wf] = 0
         for z in nodes:
             if not z["built"]:
                 continue
@@ -1222,18 +1370,39 @@ class TreeTrainer:
             hg.index_add_(0, idx, qg.unsqueeze(1).expand(-1, F).reshape(-1))
             hist[z["slot"], 0] = hw.view(F, NB)
             hist[z["slot"], 1] = hg.view(F, NB)
+            if wide is not None:    # every level on the scale_g grid (no u32 root mode for wide features)
+                qg = torch.round((w[rows] * g[rows]).float().double() * self.scale_g).long()
+                for j in range(self.Fw):
+                    cb = wcodes[rows % d.n, j]
+                    wide["hist"][z["slot"], 0, j].index_add_(0, cb, qw)
+                    wide["hist"][z["slot"], 1, j].index_add_(0, cb, qg)
         if n_built:
             self._hist_allreduce(hist[:n_built])
+            if wide is not None:
+                self._hist_allreduce(wide["hist"][:n_built])
         for z in nodes:
             if not z["built"]:
                 hist[z["slot"]] = hist_prev[z["parent"]] - hist[z["sib_slot"]]
+                if wide is not None:
+                    wide["hist"][z["slot"]] = wide["prev"][z["parent"]] - wide["hist"][z["sib_slot"]]
         cand = torch.zeros(nn, F, 8, dtype=torch.float32)
         cat_order = np.zeros((nn, F, NB), dtype=np.uint8) if d.is_cat.any() else None
+        if wide is not None and d.is_cat[d.wide_feats].any():
+            wide["cat_order"] = np.zeros((nn, self.Fw, self.nbp), dtype=np.uint16)
         HW = hist[:, 0].double() * (1.0 / self.scale_w)
         HG = hist[:, 1].double() * (1.0 / self.scale_g)
         for s_ in range(nn):
             for f in range(F):
                 if mask is not None and not mask[s_, f]:
+                    continue
+                if d.wide_of[f] >= 0:
+                    j = int(d.wide_of[f])
+                    row, order = self._scan_wide_cpu(wide["hist"][s_, 0, j].numpy(), wide["hist"][s_, 1, j].numpy(),
+                                                     int(d.nbins[f]), bool(d.is_cat[f]), imp, min_inst, min_gain)
+                    if row is not None:
+                        cand[s_, f] = torch.tensor(row)
+                    if d.is_cat[f]:
+                        wide["cat_order"][s_, j] = order
                     continue
                 cw = HW[s_, f].clone()
                 cs = HG[s_, f].clone()
@@ -1262,6 +1431,33 @@ class TreeTrainer:
                     cand[s_, f] = torch.tensor([best, bb, lw, ls, tw - lw, ts - ls, 1.0, tw])
         return self._select_best(cand, nn), cat_order
 
+    def _scan_wide_cpu(self, qw, qg, nb, cat, imp, min_inst, min_gain):
+        """One (node, wide feature) split scan as gbdt_split_wide_kernel does it: categorical bins
+        ordered by s / w (stable, empty bin 4.9e-324, bins >= nb last), int64 prefix sums over the
+        ordered bins, one conversion to double per candidate.  Returns (cand row or None, order)."""
+        inv_w, inv_g = 1.0 / self.scale_w, 1.0 / self.scale_g
+        order = np.arange(len(qw))
+        if cat:
+            cw, cs = qw[:nb].astype(np.float64) * inv_w, qg[:nb].astype(np.float64) * inv_g
+            key = np.full(len(qw), 1e300)
+            key[:nb] = np.where(cw != 0, cs / np.where(cw != 0, cw, 1.0), 4.9e-324)
+            order = np.argsort(key, kind="stable")
+        pw, ps = np.cumsum(qw[order]), np.cumsum(qg[order])
+        tw, ts = float(pw[-1]) * inv_w, float(ps[-1]) * inv_g
+        best, bb = -1.0, -1
+        for b in range(nb - 1):
+            lw, ls = float(pw[b]) * inv_w, float(ps[b]) * inv_g
+            rw, rs = tw - lw, ts - ls
+            if lw <= min_inst or rw <= min_inst:
+                continue
+            gain = _gain_py(imp, lw, ls, rw, rs)
+            if gain > min_gain and gain > best:
+                best, bb = gain, b
+        if bb < 0:
+            return None, order
+        lw, ls = float(pw[bb]) * inv_w, float(ps[bb]) * inv_g
+        return [best, bb, lw, ls, tw - lw, ts - ls, 1.0, tw], order
+
     # ------------------------------------------------------------------------------------
     def _leaf_update(self, nodes, split_feat, split_bin, cat_left, pos2row, pos_node, leaf_vals, fuse):
         """Final level of a fused GBT tree: pred[row] += scale * value of the row's leaf (split nodes:
@@ -1275,6 +1471,10 @@ class TreeTrainer:
         self._leaf_done = True
         rb = self._root_bins()
         st = nat.stream_of(d.y)
+        if self.Fw:       # (the leaf-window kernel reads uint8 codes and 8-word sets only)
+            self._flag_wide(pos2row, pos_node, _h2d(split_feat, self.dev), _h2d(split_bin, self.dev),
+                            _h2d(cat_left.view(np.int32), self.dev), None, None, pred, leaf_vals, scale, 1)
+            return
         if LEAF_WINDOW and self._nmod == 0 and nn <= 1024:
             starts = np.array([z["start"] for z in nodes], dtype=np.int32)
             ends = np.array([z["end"] for z in nodes], dtype=np.int32)
@@ -1296,6 +1496,17 @@ class TreeTrainer:
                      pos2row, pos_node, sf, sb, cl, self.is_cat_t, None, None, self._npos, self._nmod, pred, leaf_vals[0], leaf_vals[1], leaf_vals[2], float(scale),
                      1, None, None, None, 0, st)
 
+    def _flag_wide(self, pos2row, pos_node, sf, sb, cl, fbits, wcnt, pred, lv, scale, final):
+        """shifu_gbdt_partition_flag for data with wide features: the split feature's code may come
+        from the uint16 columns, the categorical left sets are CW words.  lv: [3, nn] node / left
+        child / right child values (fused prediction update) or None."""
+        from ..ops import _native as nat
+        d = self.data
+        nat.call_hip("shifu_gbdt_partition_flag_wide", d.kbins, d.group_stride, d.wbins, d.n, self.wide_of_t,
+                     pos2row, pos_node, sf, sb, cl, self.CW, self.is_cat_t, fbits, wcnt, self._npos, self._nmod,
+                     pred, None if lv is None else lv[0], lv[1] if final else None, lv[2] if final else None,
+                     float(scale), int(final), nat.stream_of(d.y))
+
     def _partition(self, nodes, split_feat, split_bin, cat_left, pos2row, pos_node, child_slots, leaf=None):
         d = self.data
         nn = len(nodes)
@@ -1316,8 +1527,9 @@ class TreeTrainer:
                                         cat_left.view(np.int32).reshape(-1), starts.astype(np.int32),
                                         ends.astype(np.int32), child_l, child_r]), self.dev)
             sf, sb = meta[:nn], meta[nn:2 * nn]
-            cl = meta[2 * nn:10 * nn]
-            st_t, en_t, chl_t, chr_t = (meta[(10 + k) * nn:(11 + k) * nn] for k in range(4))
+            cw = self.CW                       # words per categorical left set (8 without wide features)
+            cl = meta[2 * nn:(2 + cw) * nn]
+            st_t, en_t, chl_t, chr_t = (meta[(2 + cw + k) * nn:(3 + cw + k) * nn] for k in range(4))
             # left bits, one 64-bit word per 64 positions + the words' popcounts (exclusive-scanned):
             # the inclusive left count at p is wpre[p / 64] + popcount of the word's bits <= p
             nw = (n + 63) // 64
@@ -1326,9 +1538,12 @@ class TreeTrainer:
             lv, (pred, scale) = leaf if leaf is not None else (None, (None, 0.0))
             # non-split nodes' rows get their leaf value here (fused GBT prediction update)
             rb = self._root_bins()        # feature-tiled copy when it exists
-            nat.call_hip("shifu_gbdt_partition_flag", d.kbins, d.group_stride, rb, self._root_stride() if rb is not None else 0,
-                         pos2row, pos_node, sf, sb, cl, self.is_cat_t, fbits, wcnt, n, self._nmod, pred, None if lv is None else lv[0], None, None,
-                         float(scale), 0, None, None, None, 0, st)
+            if self.Fw:
+                self._flag_wide(pos2row, pos_node, sf, sb, cl, fbits, wcnt, pred, lv, scale, 0)
+            else:
+                nat.call_hip("shifu_gbdt_partition_flag", d.kbins, d.group_stride, rb, self._root_stride() if rb is not None else 0,
+                             pos2row, pos_node, sf, sb, cl, self.is_cat_t, fbits, wcnt, n, self._nmod, pred, None if lv is None else lv[0], None, None,
+                             float(scale), 0, None, None, None, 0, st)
             wpre = torch.cumsum(wcnt, 0, dtype=torch.int32) - wcnt
             # per node: left count before its start and #left, on the device; the scatter runs
             # before the host reads the counts (the D2H overlaps it)
@@ -1382,6 +1597,11 @@ class TreeTrainer:
             from ..ops import _native as nat
             feat, thr, cl, val = tree.device_arrays(data.device)
             ic = torch.from_numpy(data.is_cat.astype(np.uint8)).to(data.device)
+            if data.n_wide:
+                nat.call_hip("shifu_gbdt_apply_tree_wide", data.kbins, data.group_stride, data.wbins, data.n,
+                             _h2d(data.wide_of, data.device), feat, thr, cl, tree.cat_left.shape[1], val, ic, pred,
+                             float(scale), int(set_mode), data.n, tree.max_nodes, nat.stream_of(pred))
+                return
             nat.call_hip("shifu_gbdt_apply_tree", data.kbins, data.group_stride, None, feat, thr, cl, val, ic,
                          pred, float(scale), int(set_mode), None, data.n, tree.max_nodes, nat.stream_of(pred))
         else:
@@ -1573,7 +1793,7 @@ class TreeTrainer:
 
     def load_state_dict(self, st: dict) -> None:
         def dec(d):
-            t = Tree(int(d["max_depth"]), float(d["weight"]))
+            t = Tree(int(d["max_depth"]), float(d["weight"]), int(d["cat_left"].shape[1]))
             t.feat, t.thr = d["feat"].numpy().copy(), d["thr"].numpy().copy()
             t.cat_left = d["cat_left"].numpy().copy().view(np.uint32)
             t.value, t.wgt_cnt = d["value"].numpy().copy(), d["wgt_cnt"].numpy().copy()
@@ -1695,6 +1915,18 @@ def _host_device_pointer(t: torch.Tensor) -> int:
     if rc != 0 or not out.value:
         raise RuntimeError(f"hipHostGetDevicePointer failed ({rc}): cannot map host-resident bins")
     return int(out.value)
+
+
+# wide-feature histogram items per level and the fewest rows of one (gbdt_hist_wide_kernel unpacks
+# every 4096 rows per LDS copy; shorter items mostly zero and write back their slab)
+WIDE_TARGET_ITEMS = 1024
+WIDE_MIN_ROWS = 16384
+
+
+def _pad_bins(nb: int) -> int:
+    """A wide feature's bins rounded up to the wide kernels' block size (pad_bins in
+    gbdt_wide_kernels.hip)."""
+    return (nb + WIDE_PAD - 1) // WIDE_PAD * WIDE_PAD
 
 
 W_BITS, G_BITS = 16, 23     # per-row fixed-point magnitude bounds (packed histogram fields)

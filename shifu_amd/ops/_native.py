@@ -101,6 +101,11 @@ HIP_SIGNATURES = {
     "shifu_gbdt_partition_scatter": "pppp" "ppp" "ppp" "pp" "pppp" "l" "pppi" "s",
     "shifu_gbdt_apply_tree": "plppppppp" "fi" "p" "li" "s",
     "shifu_gbdt_residual": "pppp" "p" "li" "s",
+    # gbdt_wide_kernels.hip (features of 257 .. 16384 bins)
+    "shifu_gbdt_hist_wide": "plp" "ppp" "i" "pipi" "dd" "l" "s",
+    "shifu_gbdt_split_wide": "ppipppp" "pi" "ppii" "pppp" "iii" "ff" "dd" "s",
+    "shifu_gbdt_partition_flag_wide": "plplp" "ppppp" "i" "ppp" "ll" "pppp" "fi" "s",
+    "shifu_gbdt_apply_tree_wide": "plplp" "ppp" "i" "ppp" "fi" "li" "s",
     # stats_kernels.hip
     "shifu_column_stats": "plppli" "ppii" "dd" "pipiip" "s",
     "shifu_normalize": "plli" "pppp" "pl" "s",

@@ -29,6 +29,7 @@
 //   * deterministic: slab order is fixed and ties break to the lowest feature, then bin, so
 //     every rank computes the identical split from the all-reduced histograms.
 #include "common.h"
+#include "gbdt_shared.h"
 #include <cstdlib>
 #include <type_traits>
 typedef __attribute__((ext_vector_type(4))) int v4i_t;
@@ -37,18 +38,12 @@ namespace {
 
 constexpr int NB = 256;        // max bins per feature (uint8 codes)
 constexpr int FG = 32;         // features per work-item group
-constexpr int QF = 128;        // features per row record (one 128-B line); 4 groups per record
 
 // XCD-aware bijective block remap: consecutive logical ids land on the same XCD (blocks b, b+8,
 // ... share an XCD under round-robin dispatch; speed only)
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
-
-// byte offset of feature f of data row `row` in the quad-blocked layout (qs = N * 128)
-__device__ __forceinline__ size_t bin_off(long qs, long row, int f) {
-  return (size_t)(f >> 7) * qs + (size_t)row * QF + (f & (QF - 1));
 }
 
 struct HistArgs {
@@ -80,15 +75,8 @@ struct HistArgs {
 constexpr int HT = 512;                       // threads per histogram block (8 waves)
 constexpr int RPP = HT / 2;                   // rows per slot pass (2 threads x 16 B per row)
 constexpr int HNE = 2 * NB * 16 / HT;         // LDS entries each thread unpacks (16)
-constexpr int PACK_G = 36;                    // low field bits (signed qg)
 
 __device__ __forceinline__ uint32_t pick(uint32_t a, uint32_t b, bool c) { return c ? b : a; }
-
-__device__ __forceinline__ void unpack_add(unsigned long long v, long long& aw, long long& ag) {
-  const long long gq = ((long long)(v << (64 - PACK_G))) >> (64 - PACK_G);
-  ag += gq;
-  aw += (long long)((v - (unsigned long long)gq) >> PACK_G);
-}
 
 // Root-level u32 modes (MODE 1 = sum w only, MODE 2 = sum w*g only): LDS u32 atomics move half
 // the bytes of the packed u64 and run at ~2x its rate (profiles/microbench_lds_atomics.txt).  The
@@ -420,8 +408,6 @@ __global__ __launch_bounds__(H6_T) void gbdt_hist64_kernel(HistArgs a, const int
 // mode 1: derived node -> hist = parent_hist - sibling_hist (sibling built this level)
 // Writes hist (fp32, for the next level's subtraction) and the best split candidate.
 // ---------------------------------------------------------------------------------------
-enum Imp : int { IMP_VARIANCE = 0, IMP_FRIEDMAN = 1, IMP_ENTROPY = 2, IMP_GINI = 3 };
-
 struct SplitArgs {
   const long long* slab;        // [n_items][2][FG][NB] int64 fixed point
   const int* node_items;        // [n_nodes][n_groups][max_items] item ids (-1 padded) (mode 0)
@@ -443,33 +429,6 @@ struct SplitArgs {
   float min_inst, min_gain;
   double inv_w, inv_g;          // 1 / fixed-point scales
 };
-
-__device__ __forceinline__ double imp_gain(int imp, double lw, double ls, double rw, double rs) {
-  const double c = lw + rw, s = ls + rs;
-  switch (imp) {
-    case IMP_FRIEDMAN: { const double d = rw * ls - lw * rs; return d * d / (lw * rw * c); }
-    case IMP_ENTROPY: {
-      auto ent = [](double n, double p1) {   // binary classes: p1 = weight of class 1
-        if (n <= 0.0) return 0.0;
-        double r1 = p1 / n, r0 = 1.0 - r1, e = 0.0;
-        if (r1 > 0.0) e -= r1 * log2(r1);
-        if (r0 > 0.0) e -= r0 * log2(r0);
-        return e;
-      };
-      return ent(c, s) - (lw / c) * ent(lw, ls) - (rw / c) * ent(rw, rs);
-    }
-    case IMP_GINI: {
-      auto gin = [](double n, double p1) {
-        if (n <= 0.0) return 0.0;
-        double r1 = p1 / n, r0 = 1.0 - r1;
-        return -(r1 * r1 + r0 * r0);
-      };
-      return gin(c, s) - (lw / c) * gin(lw, ls) - (rw / c) * gin(rw, rs);
-    }
-    default:   // variance: (sL^2/cL + sR^2/cR - s^2/c) / c  (sum-of-squares terms cancel)
-      return (ls * ls / lw + rs * rs / rw - s * s / c) / c;
-  }
-}
 
 __global__ __launch_bounds__(256) void gbdt_split_kernel(SplitArgs a) {
   __shared__ double skey[4][NB];
