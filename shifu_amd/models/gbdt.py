@@ -544,6 +544,8 @@ class TreeTrainer:
             self.timings["split"] += time.perf_counter() - t0
             lv_stat = {"level": level, "nodes": len(nodes), "built": int(n_built), "hist_rows": lv_rows,
                        "hist_split_ms": (time.perf_counter() - t0) * 1e3}
+            if "hist_passes" in hist:      # multi-class: histogram launches of the level
+                lv_stat["hist_passes"] = hist["hist_passes"]
             level_log.append(lv_stat)
             # decisions ------------------------------------------------------------------
             split_feat = np.full(len(nodes), -1, dtype=np.int32)
@@ -882,13 +884,15 @@ class TreeTrainer:
         return r_start, r_slot, rng[1], nn
 
     # ------------------------------------------------------------------------------------
-    def _make_items(self, nodes, n_built, est=False, align=1):
+    def _make_items(self, nodes, n_built, est=False, align=1, sub=1):
         """Work items [n, 4] = (node_slot, lo, hi, group) for the built nodes, chunked for
         parallelism, and node_items [n_nodes, n_groups, max_items] (item ids, -1 padded).
         Vectorized over all nodes at once (it runs on the host between two GPU launches of every
         level); order: node, quad, chunk, sub-group.  ``est``: the node sizes z["m"] are estimates
         and the row ranges live on the device -- items hold (slot, chunk, n_chunks, group) and
-        shifu_gbdt_items_fix turns them into row ranges before the histogram launch."""
+        shifu_gbdt_items_fix turns them into row ranges before the histogram launch.  ``sub``: the
+        caller cuts every item into that many sub-items, so the level is chunked for 1 / sub of
+        the item target."""
         G = self.ngroups
         Q = (G + 3) // 4
         bz = [z for z in nodes if z["built"] and _zm(z) > 0]
@@ -903,7 +907,7 @@ class TreeTrainer:
             # zeroing and slab traffic; levels 3 / 4 of the balanced bench 13.1 / 12.3 vs 13.9 /
             # 12.5 ms, levels with 8+ nodes lose with it: profiles/r6/gbdt/items_per_level_r6.txt)
             target = TARGET_ITEMS_FEW if (not getattr(self, "_root_level", True) and n_built <= 4) else TARGET_ITEMS
-            k = np.maximum(1, np.rint(target * (m / max(1, rows_built)) / G).astype(np.int64))
+            k = np.maximum(1, np.rint(target / sub * (m / max(1, rows_built)) / G).astype(np.int64))
             k = np.minimum(np.minimum(k, np.maximum(1, m // 4096)), 64)
         else:
             k = np.full(len(bz), int(self.items_per_node_group), np.int64)
@@ -1279,6 +1283,8 @@ class TreeTrainer:
         (target = one-hot of the class), the gain scan is vectorized over (node, feature, bin)."""
         cfg, d = self.cfg, self.data
         C, F, nn = cfg.n_classes, self.F, len(nodes)
+        if self._mc_plan() is not None:
+            return self._build_and_split_multi_hip(nodes, n_built, g, w, pos2row, hist_prev, mask)
         yl = g.round().long()
         hists = []
         for c in range(C):
@@ -1338,7 +1344,68 @@ class TreeTrainer:
             best.append((int(f), int(b), float(gn) if v else 0.0, float(lws), float(l1), float(rws), float(r1),
                          bool(v)))
             class_lr.append((float(cl), float(cr)))
-        return {"hist": hists, "best": best, "cat_order": cat_order, "class_lr": class_lr}
+        return {"hist": hists, "best": best, "cat_order": cat_order, "class_lr": class_lr, "hist_passes": C}
+
+    def _mc_plan(self):
+        """(nbp, FI) of the one-pass multi-class kernels (gbdt_mc_kernels.hip): the class-keyed bin
+        axis is C * nbp long, nbp = the trained features' largest bin count rounded up to a power
+        of two, and a histogram item covers FI features.  None: the C-pass path (CPU, more than
+        4096 class-keyed bins, or SHIFU_GBDT_MC_KERNEL=0)."""
+        if not hasattr(self, "_mc"):
+            self._mc = None
+            if self.gpu and os.environ.get("SHIFU_GBDT_MC_KERNEL", "1") != "0":
+                from ..ops import _native as nat
+                nbp = max(2, 1 << (int(self.data.nbins_narrow.max()) - 1).bit_length())
+                fi = nat.hip().shifu_gbdt_mc_tier(int(self.cfg.n_classes), nbp)
+                self._mc = (nbp, fi) if fi else None
+        return self._mc
+
+    def _build_and_split_multi_hip(self, nodes, n_built, g, w, pos2row, hist_prev, mask):
+        """One level of a multi-class forest on the GPU: one class-keyed histogram pass over the
+        built nodes' rows (+ slab reduction), the all-reduce, one split launch over every node."""
+        from ..ops import _native as nat
+        cfg, d = self.cfg, self.data
+        C, F, nn = cfg.n_classes, self.F, len(nodes)
+        nbp, fi = self._mc_plan()
+        st = nat.stream_of(d.y)
+        if self._root_level:        # once per tree (batch): labels outside [0, C) are in no class
+            yl = g.round()
+            self._mc_cls = torch.where((yl >= 0) & (yl < C), yl, torch.full_like(yl, 255.0)).to(torch.uint8)
+        t0 = time.perf_counter()
+        hist = torch.empty(nn, C, F, NB, dtype=torch.int64, device=self.dev)
+        if n_built:
+            S = FG // fi            # a group item's sub-items are consecutive: they share its 128-B lines
+            gi, ni, max_items = self._make_items(nodes, n_built, sub=S)
+            items = np.repeat(gi, S, axis=0)
+            items[:, 3] = items[:, 3] * S + np.tile(np.arange(S, dtype=np.int32), len(gi))
+            slab = torch.empty(max(1, len(items)) * C * nbp * fi, dtype=torch.int64, device=self.dev)
+            built = _h2d(np.asarray([z["slot"] for z in nodes if z["built"]], np.int32), self.dev)
+            nat.call_hip("shifu_gbdt_hist_mc", d.kbins, d.group_stride, None if self._root_level else pos2row, w,
+                         self._mc_cls, _h2d(items, self.dev), len(items), slab, _h2d(ni, self.dev), max_items,
+                         built, n_built, hist, C, F, nbp, self.scale_g, self._nmod, st)
+            self.timings["hist"] += time.perf_counter() - t0
+            self._hist_allreduce(hist[:n_built])
+        par = np.full(nn, -1, np.int32)
+        sib = np.zeros(nn, np.int32)
+        for z in nodes:
+            if not z["built"]:
+                par[z["slot"]], sib[z["slot"]] = z["parent"], z["sib_slot"]
+        cat = bool(d.is_cat.any())
+        cand = torch.empty(nn, F, 10, dtype=torch.float64, device=self.dev)
+        order = torch.empty(nn, F, NB, dtype=torch.uint8, device=self.dev) if cat else None
+        best_t = torch.empty(nn, 10, dtype=torch.float64, device=self.dev)
+        order_t = torch.empty(nn, NB, dtype=torch.uint8, device=self.dev) if cat else None
+        nat.call_hip("shifu_gbdt_split_mc", hist, hist_prev, _h2d(par, self.dev), _h2d(sib, self.dev), nn,
+                     self.nbins_t, self.is_cat_t, mask, cand, order, C, F, nbp, IMPURITY_IDS[cfg.impurity],
+                     float(cfg.min_instances_per_node), float(cfg.min_info_gain), 1.0 / self.scale_g, best_t,
+                     order_t, st)
+        res = best_t.cpu().numpy()
+        best = [(int(r[0]), int(r[1]), float(r[2]), float(r[3]), float(r[4]), float(r[5]), float(r[6]), bool(r[7]))
+                for r in res]
+        # the chosen feature's order only, read as cat_order[slot][feature]
+        co = np.broadcast_to(order_t.cpu().numpy()[:, None, :], (nn, F, NB)) if cat else None
+        return {"hist": hist, "best": best, "cat_order": co, "class_lr": [(float(r[8]), float(r[9])) for r in res],
+                "hist_passes": 1 if n_built else 0}
 
     def _build_and_split_torch(self, nodes, n_built, g, w, pos2row, hist_prev, hist, mask, imp, min_inst,
                                min_gain, wide=None):
@@ -1709,7 +1776,8 @@ class TreeTrainer:
             self.trees.append(tree)
             self.train_errors.append(terr)
             self.valid_errors.append(verr)
-            st = self.last_tree_stats if c.is_gbt else None
+            # multi-class RF: the level table (with hist_passes) of the forest batch that grew the tree
+            st = self.last_tree_stats if (c.is_gbt or c.is_multiclass) else None
             self.last_tree_stats = {"tree": tid, "ms": (time.perf_counter() - t_tree) * 1e3,
                                     "hist_rows": self.hist_rows_total - rows0,
                                     "allreduce_ms": self._allreduce_ms(),

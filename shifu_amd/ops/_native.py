@@ -106,6 +106,10 @@ HIP_SIGNATURES = {
     "shifu_gbdt_split_wide": "ppipppp" "pi" "ppii" "pppp" "iii" "ff" "dd" "s",
     "shifu_gbdt_partition_flag_wide": "plplp" "ppppp" "i" "ppp" "ll" "pppp" "fi" "s",
     "shifu_gbdt_apply_tree_wide": "plplp" "ppp" "i" "ppp" "fi" "li" "s",
+    # gbdt_mc_kernels.hip (multi-class RF: class-keyed histogram + split)
+    "shifu_gbdt_mc_tier": ("ii", "i"),
+    "shifu_gbdt_hist_mc": "plppp" "pip" "pi" "pi" "p" "iii" "d" "l" "s",
+    "shifu_gbdt_split_mc": "pppp" "i" "ppp" "pp" "iiii" "ddd" "pp" "s",
     # stats_kernels.hip
     "shifu_column_stats": "plppli" "ppii" "dd" "pipiip" "s",
     "shifu_normalize": "plli" "pppp" "pl" "s",
