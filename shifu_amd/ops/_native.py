@@ -44,7 +44,6 @@ HIP_SIGNATURES = {
     # sort_kernels.hip
     "shifu_sort_ws": ("l", "l"),
     "shifu_sort_desc": "plpps",
-    "shifu_gemm_set_stages": "i",
     "shifu_gemm_set_big": "i",
     "shifu_gemm_set_tune": "ii",
     "shifu_mlp_set_out_waves": "i",
@@ -72,17 +71,12 @@ HIP_SIGNATURES = {
     # gemm_ring.hip
     "shifu_wgrad_ring": "plplpl" "iii" "pl" "s",
     "shifu_wgrad_ring_ws": ("iii", "l"),
-    "shifu_ring_set_stamp": "p",
-    "shifu_ring_nt_set_lab": "ip",
-    "shifu_ring_nt_set_variant": "i",
-    "shifu_strip_nt": "plplipl" "iii" "iiiii" "s",
+    # gemm_strip_nt.hip
+    "shifu_strip_nt": "plplipl" "iii" "iiii" "s",
     # fused head + layer-below dgrad (gemm_strip_head.hip)
     "shifu_strip_head": "plpli" "pl" "plpl" "iiii" "pi" "ppppp" "iiii" "fff" "s",
     "shifu_strip_head_rows": ("i", "i"),
     "shifu_strip_head_set_dbg_rows": "p",
-    "shifu_strip_nt_set_lab": "i",
-    "shifu_ring_set_mf": "i",
-    "shifu_ring_set_dmamma": "i",
     # gbdt_kernels.hip
     "shifu_gbdt_hist": "pli" "ppp" "i" "pipi" "dd" "l" "i" "s",
     "shifu_gbdt_hist_root_quad": "plpppipids",

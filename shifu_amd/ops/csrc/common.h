@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <utility>
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8;   // MFMA 16x16x32 bf16 A/B fragment
 typedef __attribute__((ext_vector_type(4))) float f32x4;    // MFMA 16x16 accumulator fragment
@@ -9,7 +10,31 @@ typedef uint16_t bf16_t;                                     // raw bf16 bits
 
 #define SHIFU_API extern "C" __attribute__((visibility("default")))
 
+typedef __attribute__((address_space(3))) void* lds_ptr_t;  // LDS-DMA (global_load_lds) destination
+typedef __attribute__((ext_vector_type(4))) int v4i_t;      // raw buffer load/store payload
+
 static constexpr int WAVE = 64;   // CDNA wavefront: 64 lanes, never 32
+
+// XCD-aware bijective block remap: consecutive logical ids land on the same XCD (blocks b, b+8,
+// ... share an XCD under round-robin dispatch; speed only)
+__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
+  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+
+// s_barrier the scheduler may not move code across (the hand-scheduled GEMM engines)
+__device__ __forceinline__ void fenced_barrier() {
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// compile-time for: f(IdxC<0>{}), ..., f(IdxC<N-1>{}); the index is usable as a template argument
+template <int I> struct IdxC { static constexpr int v = I; };
+template <typename F, int... Is>
+__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, Is...>) { (f(IdxC<Is>{}), ...); }
+template <int N, typename F>
+__device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
 __device__ __forceinline__ float bf2f(bf16_t v) {
   return __uint_as_float(((uint32_t)v) << 16);

@@ -32,19 +32,11 @@
 #include "gbdt_shared.h"
 #include <cstdlib>
 #include <type_traits>
-typedef __attribute__((ext_vector_type(4))) int v4i_t;
 
 namespace {
 
 constexpr int NB = 256;        // max bins per feature (uint8 codes)
 constexpr int FG = 32;         // features per work-item group
-
-// XCD-aware bijective block remap: consecutive logical ids land on the same XCD (blocks b, b+8,
-// ... share an XCD under round-robin dispatch; speed only)
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
 
 struct HistArgs {
   const uint8_t* bins; long gs;      // quad-blocked bins [Q][N][128]: gs = N * 128 bytes per quad

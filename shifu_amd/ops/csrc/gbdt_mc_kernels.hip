@@ -14,7 +14,7 @@
 //                            A thread owns min(FI, 16) bytes of a row and rotates them by its lane
 //                            (as gbdt_hist_kernel) so the lanes of an LDS group always update
 //                            distinct features = distinct bank pairs whatever the keys are.  The
-//                            sub-items of one record are consecutive items: one XCD (xcd_block),
+//                            sub-items of one record are consecutive items: one XCD (xcd_remap),
 //                            every fetched line is consumed from that XCD's L2.
 //   * gbdt_reduce_mc_kernel  sums a built node's item slabs in item order and transposes them
 //                            through LDS into hist[node][C][F][256] (the all-reduced tensor).
@@ -53,7 +53,7 @@ __global__ __launch_bounds__(MT) void gbdt_hist_mc_kernel(McHistArgs a) {
   constexpr int RPP = MT / TPR;              // rows per pass
   constexpr int NW = TF / 4;                 // 32-bit words of those bytes
   extern __shared__ __attribute__((aligned(16))) unsigned long long msm[];   // [C * nbp][FI]
-  const int item = xcd_block(blockIdx.x, gridDim.x);
+  const int item = xcd_remap(blockIdx.x, gridDim.x);
   const int lo = a.items[item * 4 + 1], hi = a.items[item * 4 + 2], f0 = a.items[item * 4 + 3] * FI;
   if (f0 >= a.n_feat) return;                // padding features only: the reduction never reads it
   const int ne2 = a.C * a.nbp * FI / 2;

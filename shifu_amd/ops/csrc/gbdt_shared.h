@@ -13,13 +13,6 @@ __device__ __forceinline__ size_t bin_off(long qs, long row, int f) {
   return (size_t)(f >> 7) * qs + (size_t)row * QF + (f & (QF - 1));
 }
 
-// XCD-aware bijective block remap (the narrow kernels' xcd_remap): consecutive logical ids land
-// on the same XCD (blocks b, b+8, ... share an XCD under round-robin dispatch; speed only)
-__device__ __forceinline__ int xcd_block(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
-
 __device__ __forceinline__ void unpack_add(unsigned long long v, long long& aw, long long& ag) {
   const long long gq = ((long long)(v << (64 - PACK_G))) >> (64 - PACK_G);
   ag += gq;

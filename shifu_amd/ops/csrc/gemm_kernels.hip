@@ -18,19 +18,13 @@
 //   * the output layer (n_out <= 8) + loss + output delta + last-hidden dgrad + output
 //     wgrad are one row kernel (memory-bound, one wave per row strip).
 #include "common.h"
+#include "gemm_engines.h"
 #include <type_traits>
 
 namespace {
 
 constexpr int BM = 128, BN = 128, BK = 64, NTHR = 256;
 constexpr int TILE_BYTES = BM * BK * 2;   // 16 KiB per operand tile
-
-// XCD-aware bijective block remap: consecutive logical ids land on the same XCD
-// (blocks b, b+8, ... share an XCD under round-robin dispatch; speed only).
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
 
 // [128 rows][64 bf16] tile, 128-B rows, 16-B chunk XOR swizzle: rows 0..15 of a fragment
 // read land on 16 distinct 16-B slots of the 256-B bank row (conflict-free ds_read_b128).
@@ -51,9 +45,6 @@ __device__ __forceinline__ s16x4 ds_read_tr16_b64(const char* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
 }
 
-enum Epi : int { EPI_ACT = 0, EPI_DACT = 1, EPI_STORE = 2,
-                 EPI_F32 = 3 };   // fp32 output tile (split-bf16 fp32-accurate products: algos/varsel.py)
-
 struct GemmArgs {
   const bf16_t* A; long lda;   // [M, K] row-major
   const bf16_t* B; long ldb;   // [NB, K] row-major (rows >= NB read as 0)
@@ -72,10 +63,9 @@ struct GemmArgs {
   int segA[7], segB[7]; long seg_stride; int seg_shift;   // seg_nk = 1 << seg_shift
 };
 
-// STAGES = LDS buffers.  1: single 32 KiB buffer + register prefetch (two barriers per k-step,
-// up to 5 blocks = 5 waves/SIMD per CU -> the HBM/L2 latency of the next tile is hidden by the
-// other resident blocks); 2: classic LDS double buffer (64 KiB, 2 blocks per CU).
-template <int EPI, int ACT, int STAGES>
+// One 32 KiB LDS buffer + register prefetch: two barriers per k-step, up to 5 blocks = 5
+// waves/SIMD per CU -> the HBM/L2 latency of the next tile is hidden by the other resident blocks.
+template <int EPI, int ACT>
 __global__ __launch_bounds__(NTHR) void gemm_nt_kernel(GemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int ntn = (p.N + BN - 1) / BN;
@@ -94,9 +84,9 @@ __global__ __launch_bounds__(NTHR) void gemm_nt_kernel(GemmArgs p) {
       rb[i] = gn < p.NB ? *(const uint4*)(p.B + (size_t)gn * p.ldb + k0 + ch * 8) : make_uint4(0, 0, 0, 0);
     }
   };
-  auto swrite = [&](int buf) {
-    char* As = smem + buf * 2 * TILE_BYTES;
-    char* Bs = As + TILE_BYTES;
+  char* const As = smem;
+  char* const Bs = As + TILE_BYTES;
+  auto swrite = [&]() {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int idx = tid + i * NTHR, row = idx >> 3, ch = idx & 7;
@@ -114,13 +104,10 @@ __global__ __launch_bounds__(NTHR) void gemm_nt_kernel(GemmArgs p) {
 
   const int nk = p.K / BK;
   gload(0);
-  swrite(0);
+  swrite();
   __syncthreads();
   for (int kt = 0; kt < nk; ++kt) {
-    const int buf = STAGES == 2 ? (kt & 1) : 0;
     if (kt + 1 < nk) gload((kt + 1) * BK);        // issue next tile's HBM loads early
-    const char* As = smem + buf * 2 * TILE_BYTES;
-    const char* Bs = As + TILE_BYTES;
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const int ch = s * 4 + (lane >> 4);
@@ -135,8 +122,8 @@ __global__ __launch_bounds__(NTHR) void gemm_nt_kernel(GemmArgs p) {
         for (int j = 0; j < 4; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[i], af[j], acc[i][j], 0, 0, 0);
     }
-    if constexpr (STAGES == 1) __syncthreads();     // every wave is done reading the buffer
-    if (kt + 1 < nk) swrite(STAGES == 2 ? (buf ^ 1) : 0);
+    __syncthreads();                                // every wave is done reading the buffer
+    if (kt + 1 < nk) swrite();
     __syncthreads();
   }
 
@@ -337,7 +324,6 @@ __device__ __forceinline__ void epilogue_256(const GemmArgs& p, f32x4 (&acc)[4][
   }
 }
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef __attribute__((ext_vector_type(2))) unsigned int v2u32_t;
 // ---------------------------------------------------------------------------------------
 // 8-phase NT GEMM (256 x 256 x 64, 8 waves 2 M x 4 N, wave tile 128 x 64, 1 block per CU).
@@ -364,7 +350,6 @@ typedef __attribute__((ext_vector_type(2))) unsigned int v2u32_t;
 // into the buffer that is not read any more, so the counted waits stay exact.
 // ---------------------------------------------------------------------------------------
 constexpr int G8_T = 512, G8_HALF = 16384, G8_BUF = 4 * G8_HALF;
-typedef __attribute__((ext_vector_type(4))) int v4i_t;
 
 // Per-thread LDS-DMA source offsets of tile (m0, n0): half-tile h (0 A-top, 1 A-bot, 2 B-0, 3 B-1),
 // instruction i (2 per thread): LDS byte P = i*8192 + wid*1024 + lane*16 of the half-tile holds
@@ -467,43 +452,40 @@ __device__ __forceinline__ void gemm8_loop(const GemmArgs& p, f32x4 (&acc)[4][8]
             a_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bq[s_][c], af[t][c], a_, 0, 0, 0);
         }
   };
-#define G8_BAR() do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); \
-                      __builtin_amdgcn_sched_barrier(0); } while (0)
 #define G8_MMA(mh, nh, bq, on) do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
     if ((on) && !(p.dbg & 64)) { __builtin_amdgcn_s_setprio(1); mma(mh, nh, bq); __builtin_amdgcn_s_setprio(0); } } while (0)
 
   // even k-tile 0 landed (its 8 DMAs are the oldest), odd k-tile 1 B halves stay in flight
   asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  G8_BAR();
-  if (wr == 1) G8_BAR();                      // stagger the two wave rows by one barrier
+  fenced_barrier();
+  if (wr == 1) fenced_barrier();              // stagger the two wave rows by one barrier
 
   for (int ke = 0; ke < nk; ke += 2) {
     const int ko = ke + 1;
     const bool odd_on = ko < nk;
     // ---- even k-tile (buffer 0)
     dma(0, ko); readB(0, 0, bf0); readA(0, 0);                                   // P1
-    G8_BAR(); G8_MMA(0, 0, bf0, true); G8_BAR();
+    fenced_barrier(); G8_MMA(0, 0, bf0, true); fenced_barrier();
     dma(1, ko); readB(0, 1, bf1); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // P2
-    G8_BAR(); G8_MMA(0, 1, bf1, true); G8_BAR();
+    fenced_barrier(); G8_MMA(0, 1, bf1, true); fenced_barrier();
     dma(2, ke + 2); readA(0, 1);                                                 // P3
-    G8_BAR(); G8_MMA(1, 1, bf1, true); G8_BAR();
+    fenced_barrier(); G8_MMA(1, 1, bf1, true); fenced_barrier();
     dma(3, ke + 2); asm volatile("s_waitcnt vmcnt(4)" ::: "memory");            // P4
-    G8_BAR(); G8_MMA(1, 0, bf0, true); G8_BAR();
+    fenced_barrier(); G8_MMA(1, 0, bf0, true); fenced_barrier();
     // ---- odd k-tile (buffer 1)
     dma(0, ke + 2); readB(1, 0, bf0); readA(1, 0);                               // P5
-    G8_BAR(); G8_MMA(0, 0, bf0, odd_on); G8_BAR();
+    fenced_barrier(); G8_MMA(0, 0, bf0, odd_on); fenced_barrier();
     dma(1, ke + 2); readB(1, 1, bf1); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // P6
-    G8_BAR(); G8_MMA(0, 1, bf1, odd_on); G8_BAR();
+    fenced_barrier(); G8_MMA(0, 1, bf1, odd_on); fenced_barrier();
     dma(2, ko + 2); readA(1, 1);                                                 // P7
-    G8_BAR(); G8_MMA(1, 1, bf1, odd_on); G8_BAR();
+    fenced_barrier(); G8_MMA(1, 1, bf1, odd_on); fenced_barrier();
     dma(3, ko + 2); asm volatile("s_waitcnt vmcnt(4)" ::: "memory");            // P8
-    G8_BAR(); G8_MMA(1, 0, bf0, odd_on); G8_BAR();
+    fenced_barrier(); G8_MMA(1, 0, bf0, odd_on); fenced_barrier();
   }
-  if (wr == 0) G8_BAR();                      // re-align the rows
+  if (wr == 0) fenced_barrier();              // re-align the rows
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // drain the trailing prefetches
-  G8_BAR();
+  fenced_barrier();
 #undef G8_MMA
-#undef G8_BAR
 }
 
 __device__ __forceinline__ void gemm8_mainloop(const GemmArgs& p, f32x4 (&acc)[4][8], int m0, int n0, char* smem) {
@@ -727,7 +709,6 @@ struct WgradArgs {
   int nsplit, interleave;      // interleave: split s takes the 64-row steps s, s+nsplit, ...
 };
 
-template <int STAGES>
 __global__ __launch_bounds__(NTHR) void wgrad_tn_kernel(WgradArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tiles_n = (p.Nv + WT_BN - 1) / WT_BN, tiles_k = p.Kx / WT_BK;
@@ -756,9 +737,9 @@ __global__ __launch_bounds__(NTHR) void wgrad_tn_kernel(WgradArgs p) {
       rx[i] = ok ? *(const uint4*)(p.X + (size_t)gm * p.ldx + k0 + ch * 8) : make_uint4(0, 0, 0, 0);
     }
   };
-  auto swrite = [&](int buf) {
-    char* Ds = smem + buf * 2 * WT_TILE;
-    char* Xs = Ds + WT_TILE;
+  char* const Ds = smem;
+  char* const Xs = Ds + WT_TILE;
+  auto swrite = [&]() {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int idx = tid + i * NTHR, row = idx >> 4, ch = idx & 15;
@@ -778,13 +759,10 @@ __global__ __launch_bounds__(NTHR) void wgrad_tn_kernel(WgradArgs p) {
   const int g = lane >> 4, tq = (lane & 15) >> 2, tp = lane & 3;
   const int nsteps = (mend - mbeg + mstride - 1) / mstride;
   gload(mbeg);
-  swrite(0);
+  swrite();
   __syncthreads();
   for (int st = 0; st < nsteps; ++st) {
-    const int buf = STAGES == 2 ? (st & 1) : 0;
     if (st + 1 < nsteps) gload(mbeg + (st + 1) * mstride);
-    const char* Ds = smem + buf * 2 * WT_TILE;
-    const char* Xs = Ds + WT_TILE;
 #pragma unroll
     for (int s = 0; s < 2; ++s) {          // two 32-row k-substeps
       bf16x8 af[4], bfr[4];
@@ -809,8 +787,8 @@ __global__ __launch_bounds__(NTHR) void wgrad_tn_kernel(WgradArgs p) {
         for (int j = 0; j < 4; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
     }
-    if constexpr (STAGES == 1) __syncthreads();
-    if (st + 1 < nsteps) swrite(STAGES == 2 ? (buf ^ 1) : 0);
+    __syncthreads();
+    if (st + 1 < nsteps) swrite();
     __syncthreads();
   }
   // acc[i][j]: D_out[n][k]: k = lane&15 (+16j), n = 4*(lane>>4) + r (+16i)
@@ -909,28 +887,17 @@ __global__ __launch_bounds__(G8_T, 1) void corr_i8_kernel(CorrArgs c) {
 // =======================================================================================
 #define CHECK_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return (int)e_; } while (0)
 
-static int g_stages = 1;     // LDS stages of the MLP GEMMs (A/B switch for tuning; 1 = default)
 static int g_big = 0;        // large-M path: 0 = auto (8-phase for M >= 64K, N >= 512, K >= 512; else 128x128),
                              // 3 = 8-phase whenever M >= 64K and N >= 256, 4 = 128x128 only
 static int g_wg_interleave = 1;   // wgrad row splits: 1 interleaved 64-row steps (-3% wgrad1 at 1M rows), 0 contiguous
 static int g_dbg = 0;             // lab ablation bits (GemmArgs::dbg)
 static int g_ring_nt = 1;         // persistent ring forward (gemm_ring_nt.hip, tune key 12; 2.2 vs 2.3-2.5 ms
                                   // for the 8-phase per-tile kernel per 2M-row chunk, profiles/r5)
-static int g_ring_nt_cap = 0;     // lab: grid cap of the ring forward (tune key 13; 0 = one block per CU)
 static int g_strip_nt = 1;        // row-strip forward engine (gemm_strip_nt.hip, tune key 14): 1 = before the ring
-// gemm_ring_nt.hip (same library): -1 when the shape is not one it takes
-extern "C" int shifu_ring_nt(const void* A, long lda, const void* B, long ldb, int NB, void* C, long ldc, int M,
-                             int N, int K, int epi, int act, int n_valid, int bias_col, int grid_cap,
-                             hipStream_t stream);
-extern "C" int shifu_strip_nt(const void* A, long lda, const void* B, long ldb, int NB, void* C, long ldc, int M,
-                              int N, int K, int epi, int act, int n_valid, int bias_col, int grid_cap,
-                              hipStream_t stream);
-SHIFU_API int shifu_gemm_set_stages(int s) { g_stages = (s == 2) ? 2 : 1; return 0; }
 SHIFU_API int shifu_gemm_set_tune(int key, int val) {
   if (key == 2) { g_wg_interleave = val; return 0; }
   if (key == 9) { g_dbg = val; return 0; }
   if (key == 12) { g_ring_nt = val; return 0; }
-  if (key == 13) { g_ring_nt_cap = val; return 0; }
   if (key == 14) { g_strip_nt = val; return 0; }
   return -1;
 }
@@ -945,12 +912,11 @@ SHIFU_API int shifu_gemm_nt(const void* A, long lda, const void* B, long ldb, in
   GemmArgs p{(const bf16_t*)A, lda, (const bf16_t*)B, ldb, (bf16_t*)C, ldc, (bf16_t*)C2, ldc2,
              (const bf16_t*)H, ldh, (const bf16_t*)Hd, ldhd, M, N, K, NB, n_valid, act, bias_col, flat, g_dbg};
   const int grid = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  const size_t lds = 2 * g_stages * TILE_BYTES;
+  const size_t lds = 2 * TILE_BYTES;
   if (act < 0 || act > 9 || epi < 0 || epi > 3) return -2;
   if (epi == EPI_F32) {             // fp32 tile out: the 128 x 128 kernel (ldc counted in floats)
     if (ldc % 4) return -1;
-    if (g_stages == 2) hipLaunchKernelGGL((gemm_nt_kernel<EPI_F32, 2, 2>), dim3(grid), dim3(NTHR), lds, stream, p);
-    else hipLaunchKernelGGL((gemm_nt_kernel<EPI_F32, 2, 1>), dim3(grid), dim3(NTHR), lds, stream, p);
+    hipLaunchKernelGGL((gemm_nt_kernel<EPI_F32, 2>), dim3(grid), dim3(NTHR), lds, stream, p);
     CHECK_HIP(hipGetLastError());
     return 0;
   }
@@ -963,13 +929,11 @@ SHIFU_API int shifu_gemm_nt(const void* A, long lda, const void* B, long ldb, in
   // 1.23 ms per 2M-row chunk (profiles/r5/NOTES_r5.md) -- with K = 256 a tile has 8 k-steps, and
   // the H round trip at every tile end is exposed.
   if (g_strip_nt && M >= 65536 && (epi == EPI_STORE || (epi == EPI_ACT && dfo_act)) && !g_dbg) {
-    const int r = shifu_strip_nt(A, lda, B, ldb, NB, C, ldc, M, N, K, epi, act, n_valid, bias_col, g_ring_nt_cap,
-                                 stream);
+    const int r = shifu_strip_nt(A, lda, B, ldb, NB, C, ldc, M, N, K, epi, act, n_valid, bias_col, stream);
     if (r != -1) return r;          // -1: shape not taken, fall through
   }
   if (g_ring_nt && M >= 65536 && (epi == EPI_STORE || (epi == EPI_ACT && dfo_act)) && !g_dbg) {
-    const int r = shifu_ring_nt(A, lda, B, ldb, NB, C, ldc, M, N, K, epi, act, n_valid, bias_col, g_ring_nt_cap,
-                                stream);
+    const int r = shifu_ring_nt(A, lda, B, ldb, NB, C, ldc, M, N, K, epi, act, n_valid, bias_col, stream);
     if (r != -1) return r;          // -1: shape not taken, fall through
   }
   const bool auto8 = g_big == 0 && M >= 65536 && N >= 512 && K >= 512;
@@ -988,9 +952,7 @@ SHIFU_API int shifu_gemm_nt(const void* A, long lda, const void* B, long ldb, in
     CHECK_HIP(hipGetLastError());
     return 0;
   }
-#define GEMM_L(E, A) do { if (g_stages == 2) \
-    hipLaunchKernelGGL((gemm_nt_kernel<E, A, 2>), dim3(grid), dim3(NTHR), lds, stream, p); \
-  else hipLaunchKernelGGL((gemm_nt_kernel<E, A, 1>), dim3(grid), dim3(NTHR), lds, stream, p); } while (0)
+#define GEMM_L(E, A) hipLaunchKernelGGL((gemm_nt_kernel<E, A>), dim3(grid), dim3(NTHR), lds, stream, p)
 #define GEMM_ACTS(E) switch (act) { case 0: GEMM_L(E, 0); break; case 1: GEMM_L(E, 1); break; \
     case 2: GEMM_L(E, 2); break; case 3: GEMM_L(E, 3); break; case 4: GEMM_L(E, 4); break; \
     case 5: GEMM_L(E, 5); break; case 6: GEMM_L(E, 6); break; case 7: GEMM_L(E, 7); break; \
@@ -1092,10 +1054,7 @@ SHIFU_API int shifu_wgrad_tn(const void* D, long ldd, const void* X, long ldx, f
   splits = (M + rps - 1) / rps;
   WgradArgs p{(const bf16_t*)D, ldd, (const bf16_t*)X, ldx, G, ldg, M, Nv, Kx, rps, splits, g_wg_interleave};
   const int ntiles = ((Nv + WT_BN - 1) / WT_BN) * (Kx / WT_BK);
-  if (g_stages == 2)
-    hipLaunchKernelGGL(wgrad_tn_kernel<2>, dim3(ntiles * splits), dim3(NTHR), 4 * WT_TILE, stream, p);
-  else
-    hipLaunchKernelGGL(wgrad_tn_kernel<1>, dim3(ntiles * splits), dim3(NTHR), 2 * WT_TILE, stream, p);
+  hipLaunchKernelGGL(wgrad_tn_kernel, dim3(ntiles * splits), dim3(NTHR), 2 * WT_TILE, stream, p);
   CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -30,22 +30,13 @@
 // in-flight registers (the lesson of gemm_strip_nt.hip; tools/asm_vmcnt_audit.py checks the ISA).
 #include "common.h"
 #include <type_traits>
-#include <utility>
 
 namespace {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef __attribute__((ext_vector_type(4))) int v4i_t;
 
 constexpr int SH_T = 512;
 constexpr int SH_NSLOT = 4;
 constexpr int SH_SLOT = 32768;                    // one step's B image
 constexpr int SH_LDS = SH_NSLOT * SH_SLOT + 1024 + 8192 + 8192;   // + output weights, gWo / error partials
-
-__device__ __forceinline__ int sh_xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
 
 template <int OFF>
 __device__ __forceinline__ bf16x8 sh_read(uint32_t a) {
@@ -83,12 +74,6 @@ __device__ __forceinline__ f32x4 sh_read_w(uint32_t a) {
   return v;
 }
 
-template <int I> struct ShIC { static constexpr int v = I; };
-template <typename F, int... Is>
-__device__ __forceinline__ void sh_for_impl(F&& f, std::integer_sequence<int, Is...>) { (f(ShIC<Is>{}), ...); }
-template <int N, typename F>
-__device__ __forceinline__ void sh_for(F&& f) { sh_for_impl(f, std::make_integer_sequence<int, N>{}); }
-
 struct StripHeadArgs {
   const bf16_t* H; long ldh;     // [M, K1] layer-below activations: head GEMM input and DACT operand
   const bf16_t* W; long ldw;     // [NB, K1] head weights (bf16)
@@ -113,7 +98,7 @@ __global__ __launch_bounds__(SH_T, 2) void strip_head_kernel(StripHeadArgs p) {
   constexpr int S = 2 * NKF;                         // steps per tile: NKF forward + NKF dgrad
   static_assert(NKF >= 4 && (S % SH_NSLOT) == 0, "step slots are static: S % 4 == 0");
   const int G = gridDim.x;
-  const int lb = sh_xcd_remap(blockIdx.x, G);
+  const int lb = xcd_remap(blockIdx.x, G);
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wid_u = __builtin_amdgcn_readfirstlane(wid);
   const int lr = lane & 15, lq = lane >> 4;
@@ -207,8 +192,6 @@ __global__ __launch_bounds__(SH_T, 2) void strip_head_kernel(StripHeadArgs p) {
   // vm ops in group ss (DMA pieces + asm loads)
   constexpr auto gsize = [](int ss) constexpr { return ss < NKF ? (ss == 0 ? 10 : 8) : 4; };
 
-#define SH_BAR() do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); \
-                      __builtin_amdgcn_sched_barrier(0); } while (0)
   // waits carry no operands; the statement after each names every asm-loaded register so hipcc
   // keeps them in place and orders their uses after the wait
 #define SH_KEEP() asm volatile("" \
@@ -220,10 +203,10 @@ __global__ __launch_bounds__(SH_T, 2) void strip_head_kernel(StripHeadArgs p) {
   const uint32_t lds0 = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
   // prologue: groups 0, 1 of the first tile
   const int t_first = lb < p.ntiles ? lb : 0;
-  issue(ShIC<0>{}, t_first);
-  issue(ShIC<1>{}, t_first);
+  issue(IdxC<0>{}, t_first);
+  issue(IdxC<1>{}, t_first);
   SH_VMWAIT(8);
-  SH_BAR();
+  fenced_barrier();
 
   for (int tile = lb; tile < p.ntiles; tile += G) {
     // launder the address bases once per tile: hipcc would otherwise hoist every per-step /
@@ -241,7 +224,7 @@ __global__ __launch_bounds__(SH_T, 2) void strip_head_kernel(StripHeadArgs p) {
       for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     bf16x8 d2f[8][2];                                // D2 as A fragments [k block][m block]
 
-    sh_for<S>([&](auto SS_) {
+    static_for<S>([&](auto SS_) {
       constexpr int s = decltype(SS_)::v;
       const uint32_t sb = lds0 + (uint32_t)((s % SH_NSLOT) * SH_SLOT);
       if constexpr (s < NKF) {
@@ -262,10 +245,10 @@ __global__ __launch_bounds__(SH_T, 2) void strip_head_kernel(StripHeadArgs p) {
           b[2] = sh_read<(2 * g + 1) * 2048>(f0);
           b[3] = sh_read<(2 * g + 1) * 2048>(f1);
         };
-        rg(b0, ShIC<0>{});
-        rg(b1, ShIC<1>{});
+        rg(b0, IdxC<0>{});
+        rg(b1, IdxC<1>{});
         __builtin_amdgcn_s_setprio(1);
-        sh_for<8>([&](auto Gi) {
+        static_for<8>([&](auto Gi) {
           constexpr int g = decltype(Gi)::v;
           bf16x8 (&b)[4] = (g & 1) ? b1 : b0;
           if constexpr (g < 7) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]) :: "memory");
@@ -280,12 +263,12 @@ __global__ __launch_bounds__(SH_T, 2) void strip_head_kernel(StripHeadArgs p) {
                 acc[2 * g + j][mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[2 * j + h], ar[s % 2][mb][h],
                                                                             acc[2 * g + j][mb], 0, 0, 0);
           __builtin_amdgcn_sched_barrier(0);
-          if constexpr (g + 2 < 8) rg(b, ShIC<g + 2>{});
+          if constexpr (g + 2 < 8) rg(b, IdxC<g + 2>{});
         });
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (s + 2 < S) issue(ShIC<s + 2>{}, tile);
-        else issue(ShIC<s + 2 - S>{}, tn);
+        if constexpr (s + 2 < S) issue(IdxC<s + 2>{}, tile);
+        else issue(IdxC<s + 2 - S>{}, tn);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (s == NKF - 1) {
           // ---------------- head epilogue (wave-local): A2, output, loss, D2, gWo partials
@@ -297,7 +280,7 @@ __global__ __launch_bounds__(SH_T, 2) void strip_head_kernel(StripHeadArgs p) {
           uint32_t wa = lds0 + SH_NSLOT * SH_SLOT + d.lq * 16;   // output weights nb*16 + 4lq (+ nb*64 B)
           float zp[2] = {0.f, 0.f};
           uint32_t apk[16][2][2];                        // A2 (bf16-exact) packed: half the VGPRs of acc
-          sh_for<4>([&](auto NB4) {
+          static_for<4>([&](auto NB4) {
             constexpr int q4 = decltype(NB4)::v;
             f32x4 wq[4];
             wq[0] = sh_read_w<(4 * q4 + 0) * 64>(wa);
@@ -390,7 +373,7 @@ __global__ __launch_bounds__(SH_T, 2) void strip_head_kernel(StripHeadArgs p) {
           float gp[64];
           int nvl2 = nvl;                                // fresh compares (not CSE'd with loop 1's)
           asm volatile("" : "+v"(nvl2), "+v"(wa));
-          sh_for<8>([&](auto NP) {
+          static_for<8>([&](auto NP) {
             constexpr int np = decltype(NP)::v;
             f32x4 wq[2];
             wq[0] = sh_read_w<(2 * np) * 64>(wa);
@@ -445,10 +428,10 @@ __global__ __launch_bounds__(SH_T, 2) void strip_head_kernel(StripHeadArgs p) {
               gp[j] = keep + __shfl_xor(send, m, 64);
             }
           };
-          rs(ShIC<32>{}, 8);
-          rs(ShIC<16>{}, 4);
-          rs(ShIC<8>{}, 2);
-          rs(ShIC<4>{}, 1);
+          rs(IdxC<32>{}, 8);
+          rs(IdxC<16>{}, 4);
+          rs(IdxC<8>{}, 2);
+          rs(IdxC<4>{}, 1);
           {
             const uint32_t ga = lds0 + (uint32_t)((char*)gw_s - smem) + (uint32_t)((wid * 256 + lr * 16 + 4 * lq) * 4);
             f32x4 g4;
@@ -462,7 +445,7 @@ __global__ __launch_bounds__(SH_T, 2) void strip_head_kernel(StripHeadArgs p) {
         } else {
           SH_VMWAIT(gsize((s + 2) % S));
         }
-        SH_BAR();
+        fenced_barrier();
       } else {
         // ---------------- dgrad step e: DZ1 columns 64e .. 64e + 63 = D2 [32 x 256] x W2^T slice
         constexpr int e = s - NKF;
@@ -505,10 +488,10 @@ __global__ __launch_bounds__(SH_T, 2) void strip_head_kernel(StripHeadArgs p) {
           b[2] = sh_read<off>(d2);
           b[3] = sh_read<off>(d3);
         };
-        rg(b0, ShIC<0>{});
-        rg(b1, ShIC<1>{});
+        rg(b0, IdxC<0>{});
+        rg(b1, IdxC<1>{});
         __builtin_amdgcn_s_setprio(1);
-        sh_for<8>([&](auto Gi) {
+        static_for<8>([&](auto Gi) {
           constexpr int g = decltype(Gi)::v;
           constexpr int nb = g >> 1;
           bf16x8 (&b)[4] = (g & 1) ? b1 : b0;
@@ -521,7 +504,7 @@ __global__ __launch_bounds__(SH_T, 2) void strip_head_kernel(StripHeadArgs p) {
             for (int mb = 0; mb < 2; ++mb)
               ad[nb][mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[q], d2f[4 * (g & 1) + q][mb], ad[nb][mb], 0, 0, 0);
           __builtin_amdgcn_sched_barrier(0);
-          if constexpr (g + 2 < 8) rg(b, ShIC<g + 2>{});
+          if constexpr (g + 2 < 8) rg(b, IdxC<g + 2>{});
         });
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
@@ -567,12 +550,12 @@ __global__ __launch_bounds__(SH_T, 2) void strip_head_kernel(StripHeadArgs p) {
           }
         }
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (s + 2 < S) issue(ShIC<s + 2>{}, tile);
-        else issue(ShIC<s + 2 - S>{}, tn);
+        if constexpr (s + 2 < S) issue(IdxC<s + 2>{}, tile);
+        else issue(IdxC<s + 2 - S>{}, tn);
         __builtin_amdgcn_sched_barrier(0);
         SH_KEEP();
         // group s+1 landed at the vmcnt(0) above
-        SH_BAR();
+        fenced_barrier();
       }
     });
   }
@@ -595,7 +578,6 @@ __global__ __launch_bounds__(SH_T, 2) void strip_head_kernel(StripHeadArgs p) {
   }
 #undef SH_VMWAIT
 #undef SH_KEEP
-#undef SH_BAR
 }
 
 __global__ __launch_bounds__(256) void sh_err_kernel(const double* slab, int T, double* err) {
@@ -669,12 +651,7 @@ SHIFU_API int shifu_strip_head(const void* H, long ldh, const void* W, long ldw,
 #define SH_ACTS(N_) switch (act) { case 0: SH_L(0, N_); break; case 1: SH_L(1, N_); break; \
     case 2: SH_L(2, N_); break; case 3: SH_L(3, N_); break; case 4: SH_L(4, N_); break; \
     case 7: SH_L(7, N_); break; case 9: SH_L(9, N_); break; default: return -1; }
-#ifdef SH_ONE                                        // lab builds: one instantiation
-  if (act != 0) return -1;
-  SH_L(0, 8);
-#else
   SH_ACTS(8)
-#endif
 #undef SH_ACTS
 #undef SH_L
   if (err_slab_path) hipLaunchKernelGGL(sh_err_kernel, dim3(1), dim3(256), 0, stream, err_slab, grid * 8, err);

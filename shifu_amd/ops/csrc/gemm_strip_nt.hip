@@ -40,13 +40,10 @@
 // step t-1.  (Issuing step t+2's loads between the MMA groups, with a 3-entry ring, measured the
 // same: 2.19 ms vs 2.18-2.20, strip_lab_d.)
 #include "common.h"
+#include "gemm_engines.h"
 #include <type_traits>
-#include <utility>
 
 namespace {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef __attribute__((ext_vector_type(4))) int v4i_t;
 
 constexpr int SN_T = 512;
 constexpr int SN_D = 2;                      // k-steps ahead: step t issues the loads of step t+D
@@ -54,12 +51,6 @@ constexpr int SN_P = SN_D;                   // A ring entries = unroll (entry t
 constexpr int SN_NSLOT = SN_D + 2;           // B slots: + the slot being read + the one landed
 constexpr int SN_SLOT = 256 * 128;           // 32 KiB: B image [256 rows][64 bf16]
 constexpr int SN_LDS = SN_NSLOT * SN_SLOT;   // 128 KiB
-enum { SN_EPI_ACT = 0, SN_EPI_STORE = 2 };   // same codes as gemm_kernels.hip's Epi
-
-__device__ __forceinline__ int sn_xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
 
 template <int OFF>
 __device__ __forceinline__ bf16x8 sn_read(uint32_t a) {
@@ -74,27 +65,19 @@ __device__ __forceinline__ void sn_gload(bf16x8& v, const void* p) {
   asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "+v"(v) : "v"(p), "n"(OFF) : "memory");
 }
 
-template <int I> struct SnIC { static constexpr int v = I; };
-template <typename F, int... Is>
-__device__ __forceinline__ void sn_for_impl(F&& f, std::integer_sequence<int, Is...>) { (f(SnIC<Is>{}), ...); }
-template <int N, typename F>
-__device__ __forceinline__ void sn_for(F&& f) { sn_for_impl(f, std::make_integer_sequence<int, N>{}); }
-
 struct StripArgs {
   const bf16_t* A; long lda;   // [M, K]
   const bf16_t* B; long ldb;   // [NB, K] (rows >= NB read row NB-1; those columns are overwritten)
   bf16_t* C; long ldc;         // [M, N]
   int M, N, K, NB, n_valid, bias_col;
   int ntiles;                  // ceil(M / 256) * ceil(N / 256)
-  int dbg;                     // LAB builds only: 1 no epilogue, 4 no MFMAs (operands kept live),
-                               // 8 no B LDS-DMA, 16 no A loads (timing ablations: results invalid)
 };
 
-template <int EPI, int ACT, bool LAB>
+template <int EPI, int ACT>
 __global__ __launch_bounds__(SN_T, 2) void strip_nt_kernel(StripArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int G = gridDim.x;
-  const int lb = sn_xcd_remap(blockIdx.x, G);
+  const int lb = xcd_remap(blockIdx.x, G);
   if (lb >= p.ntiles) return;                        // whole block
   const int ntn = (p.N + 255) >> 8;
   const int nk = p.K >> 6;
@@ -140,14 +123,10 @@ __global__ __launch_bounds__(SN_T, 2) void strip_nt_kernel(StripArgs p) {
     }
   };
   auto issue = [&](int slot, bf16x8 (&a)[2][2]) __attribute__((always_inline)) {
-    if (!(LAB && (p.dbg & 8))) {                     // LAB dbg 8: no B LDS-DMA pieces
 #pragma unroll
-      for (int i = 0; i < 4; ++i) issue_dma(slot, i);
-    }
-    if (!(LAB && (p.dbg & 16))) {                    // LAB dbg 16: no A loads
-      issue_a(a, 0);
-      issue_a(a, 1);
-    }
+    for (int i = 0; i < 4; ++i) issue_dma(slot, i);
+    issue_a(a, 0);
+    issue_a(a, 1);
     advance();
   };
 
@@ -180,12 +159,12 @@ __global__ __launch_bounds__(SN_T, 2) void strip_nt_kernel(StripArgs p) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float z = acc[2 * np + s][mb][r];
-            const float a = EPI == SN_EPI_ACT ? act_fwd(ACT, z) : z;
+            const float a = EPI == EPI_ACT ? act_fwd(ACT, z) : z;
             if constexpr (decltype(FULL)::value) {
               o[r] = a;
             } else {                                 // branch-free column masks
               const int n = n0 + (2 * np + s) * 16 + 4 * lq + r;
-              if constexpr (EPI == SN_EPI_ACT) o[r] = n < p.n_valid ? a : ((n == p.n_valid && p.bias_col) ? 1.f : 0.f);
+              if constexpr (EPI == EPI_ACT) o[r] = n < p.n_valid ? a : ((n == p.n_valid && p.bias_col) ? 1.f : 0.f);
               else o[r] = n < p.NB ? a : 0.f;
             }
           }
@@ -210,12 +189,7 @@ __global__ __launch_bounds__(SN_T, 2) void strip_nt_kernel(StripArgs p) {
   };
   auto epilogue = [&](int t) __attribute__((always_inline)) {
     const int n0 = (t % ntn) * 256;
-    if (LAB && (p.dbg & 1)) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) asm volatile("" :: "v"(acc[i][j]));
-    } else if (n0 + 256 <= (EPI == SN_EPI_ACT ? p.n_valid : p.NB)) {
+    if (n0 + 256 <= (EPI == EPI_ACT ? p.n_valid : p.NB)) {
       store_tile(t, std::integral_constant<bool, true>{});
     } else {
       store_tile(t, std::integral_constant<bool, false>{});
@@ -226,8 +200,6 @@ __global__ __launch_bounds__(SN_T, 2) void strip_nt_kernel(StripArgs p) {
       for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   };
 
-#define SN_BAR() do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); \
-                      __builtin_amdgcn_sched_barrier(0); } while (0)
   // Every vmcnt wait names EVERY A ring register ("+v"): an asm load's destination counts as
   // written at the asm statement, so a loaded value that no later statement reads (the last
   // re-issued steps past the end of the sequence) would be dead to hipcc and its registers handed
@@ -243,24 +215,19 @@ __global__ __launch_bounds__(SN_T, 2) void strip_nt_kernel(StripArgs p) {
   static_assert(SN_P == 2, "SN_WAIT_A names a 2-entry ring");
 
   // prologue: steps 0 .. D-1 in flight
-  sn_for<SN_D>([&](auto I) { issue(I.v, ar[I.v]); });
+  static_for<SN_D>([&](auto I) { issue(I.v, ar[I.v]); });
   SN_WAIT_A(8, 0);
-  SN_BAR();
+  fenced_barrier();
 
   // B fragments of n blocks 2g, 2g+1 (both k halves) x the wave's A fragments: 8 MFMAs, k ascending
   auto mma = [&](const bf16x8 (&b)[4], int g, const bf16x8 (&a)[2][2]) __attribute__((always_inline)) {
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        if (LAB && (p.dbg & 4)) {
-          asm volatile("" :: "v"(b[2 * j + h]), "v"(a[0][h]), "v"(a[1][h]));
-        } else {
+      for (int h = 0; h < 2; ++h)
 #pragma unroll
-          for (int mb = 0; mb < 2; ++mb)
-            acc[2 * g + j][mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[2 * j + h], a[mb][h], acc[2 * g + j][mb], 0, 0, 0);
-        }
-      }
+        for (int mb = 0; mb < 2; ++mb)
+          acc[2 * g + j][mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[2 * j + h], a[mb][h], acc[2 * g + j][mb], 0, 0, 0);
   };
   // group g: fragments (nb 2g, h 0), (2g, 1), (2g+1, 0), (2g+1, 1)
   auto read_group = [&](bf16x8 (&b)[4], uint32_t sb, auto G_) __attribute__((always_inline)) {
@@ -274,29 +241,29 @@ __global__ __launch_bounds__(SN_T, 2) void strip_nt_kernel(StripArgs p) {
                                      :: "memory")
   int kk = 0, tile = lb, since_epi = 0, rslot = 0, dslot = SN_D;
   for (int t0 = 0; t0 < T; t0 += SN_P) {          // T is a multiple of 2 (K % 128 == 0)
-    sn_for<SN_P>([&](auto E) {
+    static_for<SN_P>([&](auto E) {
       constexpr int e = E.v;
       const int t = t0 + e;
       const uint32_t sb = lds0 + (uint32_t)(rslot * SN_SLOT);
       bf16x8 b0[4], b1[4];
       {
-        read_group(b0, sb, SnIC<0>{});
-        read_group(b1, sb, SnIC<1>{});
+        read_group(b0, sb, IdxC<0>{});
+        read_group(b1, sb, IdxC<1>{});
         __builtin_amdgcn_s_setprio(1);
-        sn_for<8>([&](auto Gi) {
+        static_for<8>([&](auto Gi) {
           constexpr int g = Gi.v;
           if constexpr ((g & 1) == 0) {
             if constexpr (g < 7) SN_WAIT_B(4, b0); else SN_WAIT_B(0, b0);
             __builtin_amdgcn_sched_barrier(0);
             mma(b0, g, ar[e]);
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (g + 2 < 8) read_group(b0, sb, SnIC<g + 2>{});
+            if constexpr (g + 2 < 8) read_group(b0, sb, IdxC<g + 2>{});
           } else {
             if constexpr (g < 7) SN_WAIT_B(4, b1); else SN_WAIT_B(0, b1);
             __builtin_amdgcn_sched_barrier(0);
             mma(b1, g, ar[e]);
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (g + 2 < 8) read_group(b1, sb, SnIC<g + 2>{});
+            if constexpr (g + 2 < 8) read_group(b1, sb, IdxC<g + 2>{});
           }
         });
         __builtin_amdgcn_s_setprio(0);
@@ -329,30 +296,24 @@ __global__ __launch_bounds__(SN_T, 2) void strip_nt_kernel(StripArgs p) {
         asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
       }
       SN_KEEP_A();
-      SN_BAR();
+      fenced_barrier();
     });
   }
   SN_WAIT_A(0, 0);                                   // the trailing loads land before the exit
 #undef SN_WAIT_B
 #undef SN_WAIT_A
 #undef SN_KEEP_A
-#undef SN_BAR
 }
 
 }  // namespace
 
-static int g_sn_dbg = -1;                    // LAB build switch: >= 0 runs strip_nt_kernel<.., LAB>
-SHIFU_API int shifu_strip_nt_set_lab(int dbg) { g_sn_dbg = dbg; return 0; }
-
-// C ABI: returns -1 when the shape is not one this engine takes (the caller falls back).
-// epi 0 = activation (derivative computable from the output: no f'(z) side output), 2 = store z.
+// C ABI (gemm_engines.h)
 SHIFU_API int shifu_strip_nt(const void* A, long lda, const void* B, long ldb, int NB, void* C, long ldc, int M,
-                             int N, int K, int epi, int act, int n_valid, int bias_col, int grid_cap,
-                             hipStream_t stream) {
+                             int N, int K, int epi, int act, int n_valid, int bias_col, hipStream_t stream) {
   if (K % 128 || K < 128 || lda % 8 || ldb % 8 || ldc % 8 || N % 8 || M <= 0 || N <= 0 || NB <= 0) return -1;
-  if (epi != SN_EPI_ACT) return -1;                  // the store-z and tanh builds spill VGPRs: the A ring
+  if (epi != EPI_ACT) return -1;                     // the store-z and tanh builds spill VGPRs: the A ring
   if (act == 1) return -1;                           // lives in asm-loaded registers, so those stay on the ring
-  if (epi == SN_EPI_ACT && !act_deriv_from_output(act)) return -1;
+  if (epi == EPI_ACT && !act_deriv_from_output(act)) return -1;
   if (256l * ldc * 2 >= (1l << 31)) return -1;                                       // 32-bit store offsets
   if (lda < K || ldb < K || ldc < N) return -1;
   const long ntiles = (long)((M + 255) / 256) * ((N + 255) / 256);
@@ -360,23 +321,15 @@ SHIFU_API int shifu_strip_nt(const void* A, long lda, const void* B, long ldb, i
   int dev = 0, ncu = 256;
   hipGetDevice(&dev);
   hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  int grid = (int)(ntiles < ncu ? ntiles : ncu);
-  if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;
+  const dim3 g((unsigned)(ntiles < ncu ? ntiles : ncu));       // one block per CU
   StripArgs p{(const bf16_t*)A, lda, (const bf16_t*)B, ldb, (bf16_t*)C, ldc, M, N, K, NB, n_valid, bias_col,
-              (int)ntiles, g_sn_dbg};
-  const dim3 g(grid);
-  if (g_sn_dbg >= 0) {
-    if (epi == SN_EPI_ACT && act == 0)
-      hipLaunchKernelGGL((strip_nt_kernel<SN_EPI_ACT, 0, true>), g, dim3(SN_T), SN_LDS, stream, p);
-    else return -1;
-  } else {
-#define SN_L(A_) hipLaunchKernelGGL((strip_nt_kernel<SN_EPI_ACT, A_, false>), g, dim3(SN_T), SN_LDS, stream, p)
-    switch (act) {
-      case 0: SN_L(0); break; case 2: SN_L(2); break; case 3: SN_L(3); break;
-      case 4: SN_L(4); break; case 6: SN_L(6); break; case 9: SN_L(9); break; default: SN_L(7); break;
-    }
-#undef SN_L
+              (int)ntiles};
+#define SN_L(A_) hipLaunchKernelGGL((strip_nt_kernel<EPI_ACT, A_>), g, dim3(SN_T), SN_LDS, stream, p)
+  switch (act) {
+    case 0: SN_L(0); break; case 2: SN_L(2); break; case 3: SN_L(3); break;
+    case 4: SN_L(4); break; case 6: SN_L(6); break; case 9: SN_L(9); break; default: SN_L(7); break;
   }
+#undef SN_L
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }

@@ -26,7 +26,6 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1 << 20)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--stages", type=int, default=1)
     ap.add_argument("--big", type=int, default=0)
     ap.add_argument("--rounds", type=int, default=0)
     ap.add_argument("--act", default="sigmoid")
@@ -36,7 +35,6 @@ def main():
     ap.add_argument("--tune", type=lambda t: tuple(int(x) for x in t.split("=")), nargs="*")
     ap.add_argument("--out-waves", type=int, default=0)
     a = ap.parse_args()
-    nat.call_hip("shifu_gemm_set_stages", a.stages)
     nat.call_hip("shifu_gemm_set_big", a.big)
     M = a.rows
     dev = torch.device("cuda")

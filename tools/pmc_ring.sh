@@ -1,5 +1,5 @@
 #!/usr/bin/env bash
-# PMC counters of the forward GEMM kernels (tools/ring_lab.py --no-lab: 8-phase + ring variants at
+# PMC counters of the forward GEMM kernels (tools/ring_lab.py: 8-phase and ring at
 # the bench's 2M x 1024 -> 512 chunk), one counter group per rocprofv3 run (--pmc never combined with
 # tracing).  Summary: python tools/pmc_summary.py gpurun_out/pmc_ring ring0=ring_nt_kernel ...
 set -euo pipefail
@@ -17,6 +17,6 @@ groups=(
 )
 for gi in "${!groups[@]}"; do
   timeout -s KILL 120 rocprofv3 --kernel-trace --pmc ${groups[$gi]} --output-format csv -d $O/g$gi -o run -- \
-    python3 $R/tools/ring_lab.py --no-lab --rounds 1 --iters 3 "$@" > $O/g$gi.log 2>&1
+    python3 $R/tools/ring_lab.py --rounds 1 --iters 3 "$@" > $O/g$gi.log 2>&1
   echo "group $gi done"
 done

@@ -1,7 +1,6 @@
 """Forward-engine lab: the row-strip engine (gemm_strip_nt.hip, tune key 14) against the persistent
 ring (gemm_ring_nt.hip, tune key 12) -- bitwise equality on the bench shape and tail shapes, then
-interleaved timing rounds in one process (median / min ms per call), and the strip engine's LAB
-ablations (dbg 1: no epilogue, 4: no MFMAs, 5: neither).  One JSON line per measurement.
+interleaved timing rounds in one process (median / min ms per call).  One JSON line per measurement.
 
     python tools/strip_lab.py [--rows 2097152] [--iters 10] [--rounds 3]
 """
@@ -18,17 +17,15 @@ def main():
     ap.add_argument("--rows", type=int, default=1 << 21)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--dbg", type=int, nargs="*", default=[1, 4, 5])
     a = ap.parse_args()
     import torch
     from shifu_amd.ops import _native as nat
     dev = torch.device("cuda")
     st = nat.stream_of(torch.empty(1, device=dev))
 
-    def run(engine, A, B, C, M, K, N, nb, nv, act, dbg=-1):
+    def run(engine, A, B, C, M, K, N, nb, nv, act):
         nat.call_hip("shifu_gemm_set_tune", 12, 1 if engine == "ring" else 0)
         nat.call_hip("shifu_gemm_set_tune", 14, 1 if engine == "strip" else 0)
-        nat.call_hip("shifu_strip_nt_set_lab", dbg)
         nat.call_hip("shifu_gemm_nt", A, K, B, K, nb, C, N, None, 0, None, 0, None, 0, M, N, K, 0, act, nv, 1, 0.0, st)
 
     # correctness: bitwise vs the ring (same k order), plus an fp32 check on the tail shapes
@@ -59,25 +56,24 @@ def main():
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2 * a.iters)]
     flop = 2.0 * M * K * nv
 
-    def timed(eng, dbg=-1):
-        run(eng, A, B, C, M, K, N, nv, nv, 0, dbg)
+    def timed(eng):
+        run(eng, A, B, C, M, K, N, nv, nv, 0)
         torch.cuda.synchronize()
         for i in range(a.iters):
             ev[2 * i].record()
-            run(eng, A, B, C, M, K, N, nv, nv, 0, dbg)
+            run(eng, A, B, C, M, K, N, nv, nv, 0)
             ev[2 * i + 1].record()
         torch.cuda.synchronize()
         ts = sorted(ev[2 * i].elapsed_time(ev[2 * i + 1]) for i in range(a.iters))
         return ts[len(ts) // 2], ts[0]
 
-    variants = [("ring", -1), ("strip", -1), ("strip_lab0", 0)] + [(f"strip_lab_dbg{d}", d) for d in a.dbg]
     for rnd in range(a.rounds):
-        for name, dbg in variants:
-            eng = "ring" if name == "ring" else "strip"
-            med, mn = timed(eng, dbg)
-            print(json.dumps({"variant": name, "round": rnd, "ms_median": round(med, 4), "ms_min": round(mn, 4),
+        for eng in ("ring", "strip"):
+            med, mn = timed(eng)
+            print(json.dumps({"variant": eng, "round": rnd, "ms_median": round(med, 4), "ms_min": round(mn, 4),
                               "tflops_median": round(flop / med / 1e9, 1), "M": M, "K": K, "N": N}), flush=True)
-    nat.call_hip("shifu_strip_nt_set_lab", -1)
+    nat.call_hip("shifu_gemm_set_tune", 12, 1)
+    nat.call_hip("shifu_gemm_set_tune", 14, 1)
 
 
 if __name__ == "__main__":
