@@ -119,6 +119,8 @@ HIP_SIGNATURES = {
     "shifu_keyed_hist": "plpl" "lii" "d" "pp" "s",
     "shifu_tree_code": "plli" "ppp" "pi" "s",
     "shifu_tree_walk_coded": "pli" "pp" "p" "pi" "pp" "iiii" "pl" "p" "s",
+    "shifu_tree_vote_rows": ("ii", "i"),
+    "shifu_tree_vote_coded": "pli" "pp" "p" "pi" "p" "iiii" "p" "s",
     # wdl_kernels.hip
     "shifu_wdl_gather": "ipipipppppiipplppllls",
     "shifu_rowdot_bf16": "pllipps",

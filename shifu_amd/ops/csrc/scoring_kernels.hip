@@ -266,6 +266,93 @@ __global__ __launch_bounds__(256) void tree_walk_coded_kernel(TreeWalkArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------
+// Class votes of a multi-class forest (leaf value = class): the coded walk above with the fp64
+// score replaced by u32 vote counters in LDS.  A block stages its R rows' codes, walks the
+// trees of its group as tree_walk_coded_kernel does (same thread -> (row, tree) map, same
+// walk_step: identical routing) and casts one ds_add_u32 per (row, tree) into cnt[R][n_classes].
+// The block's counters are the contiguous run votes[rb * n_classes ..) of the row-major output,
+// so they are flushed with consecutive lanes on consecutive words (integer global atomics: tree
+// groups and bags add into the same table, exact in any order).  No leaf table, no fp64
+// partials, lrs not read (a vote is unweighted).
+// ---------------------------------------------------------------------------------------
+struct TreeVoteArgs {
+  TreeWalkArgs w;                           // part / leaf_out / lrs unused
+  int n_classes;
+  int* votes;                               // [n][n_classes], zeroed by the caller (or holding earlier votes)
+};
+
+constexpr int TV_LDS = 32 * 1024;           // R is sized to this (>= 4 blocks per CU); one row of the widest
+                                            // shape (16384 inputs, 255 classes) takes 33 KiB
+
+__host__ __device__ inline size_t vote_cnt_off(int R, int C) { return ((size_t)R * C * 2 + 15) & ~(size_t)15; }
+inline size_t vote_lds(int R, int C, int n_classes) { return vote_cnt_off(R, C) + (size_t)R * n_classes * 4; }
+
+// rows per block: the largest power of two <= 256 whose codes + counters fit TV_LDS, one row when
+// a single row is larger than that; 0 when the kernel cannot hold the shape
+int vote_rows(int C, int n_classes) {
+  if (C < 1 || C > 16384 || n_classes < 1 || n_classes > 255) return 0;
+  for (int R = 256; R > 1; R >>= 1)
+    if (vote_lds(R, C, n_classes) <= (size_t)TV_LDS) return R;
+  return 1;
+}
+
+__global__ __launch_bounds__(256) void tree_vote_coded_kernel(TreeVoteArgs v) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char vsm[];
+  const TreeWalkArgs& a = v.w;
+  uint16_t* rows = (uint16_t*)vsm;                                  // [R][C]
+  uint32_t* cnt = (uint32_t*)(vsm + vote_cnt_off(a.R, a.C));        // [R][n_classes]
+  const int nc = v.n_classes;
+  const long rb = (long)blockIdx.x * a.R;
+  const int nr = (int)min((long)a.R, a.n - rb);
+  const uint16_t* src = a.codes + rb * a.C;
+  for (int i = threadIdx.x; i < nr * a.C; i += 256) rows[i] = src[i];
+  for (int i = threadIdx.x; i < nr * nc; i += 256) cnt[i] = 0u;
+  __syncthreads();
+  const int TPR = 256 / a.R, r = threadIdx.x % a.R, sub = threadIdx.x / a.R;
+  const int t0 = blockIdx.y * a.tg, t1 = min(a.T, t0 + a.tg);
+  const uint16_t* row = rows + r * a.C;
+  uint32_t* mine = cnt + r * nc;
+  const double top = (double)(nc - 1);
+  if (r < nr) {
+    for (int t = t0 + sub; t < t1; t += WCH * TPR) {
+      // WCH independent chains (trees t, t + TPR, ...): a chain past the group's end repeats the
+      // last tree and casts no vote
+      int id[WCH];
+      int4 nd[WCH];
+#pragma unroll
+      for (int c = 0; c < WCH; ++c) {
+        id[c] = a.roots[min(t + c * TPR, t1 - 1)];
+        nd[c] = a.node[id[c]];
+      }
+      for (int d = 0; d < a.depth; ++d) {
+#pragma unroll
+        for (int c = 0; c < WCH; ++c)
+          if (nd[c].x >= 0) id[c] = walk_step(a, row, nd[c]);
+#pragma unroll
+        for (int c = 0; c < WCH; ++c) nd[c] = a.node[id[c]];
+      }
+      double lv[WCH];
+#pragma unroll
+      for (int c = 0; c < WCH; ++c) lv[c] = a.value[id[c]];         // WCH leaf loads in flight
+#pragma unroll
+      for (int c = 0; c < WCH; ++c) {
+        if (t + c * TPR >= t1) break;
+        // round half to even, then clamp in fp64 (a value past the int range, or NaN -> class 0,
+        // never reaches the conversion)
+        const int cls = (int)fmin(fmax(rint(lv[c]), 0.0), top);
+        atomicAdd(&mine[cls], 1u);                                  // result unused: ds_add_u32
+      }
+    }
+  }
+  __syncthreads();
+  int* out = v.votes + rb * nc;                                     // the block's rows are contiguous
+  for (int i = threadIdx.x; i < nr * nc; i += 256) {
+    const uint32_t k = cnt[i];
+    if (k) atomicAdd(&out[i], (int)k);
+  }
+}
+
+// ---------------------------------------------------------------------------------------
 // Keyed counts: out_cnt[f][k] += 1, out_w[f][k] += round(w * scale) for every row with
 // 0 <= key < K.  keys[f * ks + r] (ks = 0: one key vector shared by every column),
 // w[f * ws + r] (ws = 0: shared weights; w == nullptr: no weighted sums).
@@ -384,6 +471,31 @@ SHIFU_API int shifu_tree_walk_coded(const void* codes, long n, int C, const void
                  roots, lrs, T, depth, tg, R, part, ldp, leaf_out};
   const size_t lds = (((size_t)R * C * 2 + 15) & ~(size_t)15) + 256 * sizeof(double);
   hipLaunchKernelGGL(tree_walk_coded_kernel, dim3((unsigned)((n + R - 1) / R), n_groups), dim3(256), lds, stream, a);
+  CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// rows per block of shifu_tree_vote_coded for (C inputs, n_classes), 0: the kernel cannot hold the
+// shape (the caller sizes its tree groups by this)
+SHIFU_API int shifu_tree_vote_rows(int C, int n_classes) { return vote_rows(C, n_classes); }
+
+// votes[r][cls] += trees of the ensemble whose leaf for row r carries class cls (codes, node, catnc
+// as for shifu_tree_walk_coded; votes [n][n_classes] int32, zeroed by the caller before the first
+// ensemble that votes into it).  Leaf class = rint(value) clamped to [0, n_classes).
+SHIFU_API int shifu_tree_vote_coded(const void* codes, long n, int C, const void* node, const int* catnc,
+                                    const double* value, const void* catlut, int lut_w, const int* roots,
+                                    int T, int depth, int n_groups, int n_classes, int* votes,
+                                    hipStream_t stream) {
+  if (n <= 0 || T <= 0) return 0;
+  const int R = vote_rows(C, n_classes);
+  if (R < 1 || n_groups < 1 || n_groups > T || n_groups > 65535 || lut_w < 1 || depth < 0) return -1;
+  const int tg = (T + n_groups - 1) / n_groups;
+  if ((long)(n_groups - 1) * tg >= T) return -1;
+  if ((n + R - 1) / R > 0x7fffffffL) return -1;
+  TreeVoteArgs a{{(const uint16_t*)codes, n, C, (const int4*)node, catnc, value, (const uint8_t*)catlut, lut_w,
+                  roots, nullptr, T, depth, tg, R, nullptr, 0, nullptr}, n_classes, votes};
+  hipLaunchKernelGGL(tree_vote_coded_kernel, dim3((unsigned)((n + R - 1) / R), n_groups), dim3(256),
+                     vote_lds(R, C, n_classes), stream, a);
   CHECK_HIP(hipGetLastError());
   return 0;
 }

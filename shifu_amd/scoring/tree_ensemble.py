@@ -135,42 +135,80 @@ class FlatEnsemble:
                     torch.from_numpy(catnc).to(dev), tb_cap)
         return self._ct
 
+    @staticmethod
+    def _groups(T: int, row_blocks: int) -> int:
+        """Tree groups (grid y) of a walk: >= 2048 blocks when the trees allow, every group owns >= 1 tree."""
+        groups = max(1, min(T, -(-2048 // row_blocks)))
+        return -(-T // -(-T // groups))
+
+    def _coded_chunks(self, X: torch.Tensor, ct):
+        """Rank X against the ensemble's thresholds (tree_code kernel) in chunks of <= 2 GiB of u16
+        codes -> (codes buffer, first row, rows) per chunk; the caller walks the chunk before it
+        asks for the next one (one buffer, stream order)."""
+        from ..ops import _native
+        n = X.shape[0]
+        XT = X.to(torch.float64).t().contiguous()             # feature-major [C, N]: coalesced at the root
+        C = XT.shape[0]
+        bnd, boff, slot_cat, _, _, tb_cap = ct
+        step = min(65535 * 256, max(1, (1 << 31) // max(C, 1) // 2))   # codes chunk <= 2 GiB
+        codes = torch.empty(min(n, step), C, dtype=torch.int16, device=X.device)
+        for r0 in range(0, n, step):
+            m = min(n, r0 + step) - r0
+            # pointer offsets into the full-width buffers: no per-chunk copies
+            _native.call_hip("shifu_tree_code", XT.data_ptr() + r0 * 8, n, m, C, bnd, boff, slot_cat, codes,
+                             tb_cap, _native.stream_of(X))
+            yield codes, r0, m
+
     def _hip_walk(self, X: torch.Tensor, want_leaves: bool):
         """One kernel launch for all (row, tree) pairs of the chunk: -> (bag score, leaf ids | None)."""
         from ..ops import _native
         _native.require_gpu_native()
-        n, T = X.shape[0], int(self.roots.numel())
-        XT = X.to(torch.float64).t().contiguous()             # feature-major [C, N]: coalesced at the root
-        C = XT.shape[0]
+        n, T, C = X.shape[0], int(self.roots.numel()), X.shape[1]
         node, thr, value, lut, roots, lrs = self._hip_tables()
         ct = self._coded_tables(C) if CODED_WALK else None
+        leaf = torch.empty(n, T, dtype=torch.int32, device=X.device) if want_leaves else None
         if ct is not None:
-            bnd, boff, slot_cat, cnode, catnc, tb_cap = ct
+            cnode, catnc = ct[3], ct[4]
             R = 1 << max(0, min(8, int(np.floor(np.log2(16384 / max(C, 1))))))
-            rb = -(-n // R)
-            groups = max(1, min(T, -(-2048 // rb)))
-            groups = -(-T // -(-T // groups))
+            groups = self._groups(T, -(-n // R))
             part = torch.empty(groups, n, dtype=torch.float64, device=X.device)
-            leaf = torch.empty(n, T, dtype=torch.int32, device=X.device) if want_leaves else None
-            step = min(65535 * 256, max(1, (1 << 31) // max(C, 1) // 2))   # codes chunk <= 2 GiB
-            codes = torch.empty(min(n, step), C, dtype=torch.int16, device=X.device)
-            for r0 in range(0, n, step):
-                m = min(n, r0 + step) - r0
-                # pointer offsets into the full-width buffers: no per-chunk copies
-                _native.call_hip("shifu_tree_code", XT.data_ptr() + r0 * 8, n, m, C, bnd, boff, slot_cat, codes,
-                                 tb_cap, _native.stream_of(X))
+            for codes, r0, m in self._coded_chunks(X, ct):
                 lv = None if leaf is None else leaf.data_ptr() + r0 * T * 4
                 _native.call_hip("shifu_tree_walk_coded", codes, m, C, cnode, catnc, value, lut, lut.shape[1],
                                  roots, lrs, T, max(self.depth, 0), R, groups, part.data_ptr() + r0 * 8, n, lv,
                                  _native.stream_of(X))
             return part.sum(0), leaf
-        groups = max(1, min(T, -(-2048 // max(1, -(-n // 256)))))
-        groups = -(-T // -(-T // groups))                     # every group owns >= 1 tree
+        XT = X.to(torch.float64).t().contiguous()
+        groups = self._groups(T, max(1, -(-n // 256)))
         part = torch.empty(groups, n, dtype=torch.float64, device=X.device)
-        leaf = torch.empty(n, T, dtype=torch.int32, device=X.device) if want_leaves else None
         _native.call_hip("shifu_tree_infer", XT, n, 1, n, node, thr, value, lut, lut.shape[1], roots, lrs, T,
                          max(self.depth, 0), groups, part, leaf, _native.stream_of(X))
         return part.sum(0), leaf
+
+    @torch.no_grad()
+    def votes(self, X: torch.Tensor, n_classes: int) -> torch.Tensor:
+        """Native multi-class forest: X [N, C] float64 -> int32 [N, n_classes], the number of trees
+        whose leaf for the row carries each class (leaf value rounded half to even and clamped to
+        [0, n_classes)).  On the GPU one code + one vote kernel per codes chunk
+        (scoring_kernels.hip tree_vote_coded_kernel: counters in LDS, no leaf table)."""
+        n, T, C = X.shape[0], int(self.roots.numel()), X.shape[1]
+        if X.is_cuda and n and T and CODED_WALK:
+            from ..ops import _native
+            _native.require_gpu_native()
+            ct = self._coded_tables(C)
+            R = _native.hip().shifu_tree_vote_rows(C, n_classes) if ct is not None else 0
+            if R:
+                _, _, value, lut, roots, _ = self._hip_tables()
+                groups = self._groups(T, -(-n // R))
+                out = torch.zeros(n, n_classes, dtype=torch.int32, device=X.device)
+                for codes, r0, m in self._coded_chunks(X, ct):
+                    _native.call_hip("shifu_tree_vote_coded", codes, m, C, ct[3], ct[4], value, lut, lut.shape[1],
+                                     roots, T, max(self.depth, 0), groups, n_classes,
+                                     out.data_ptr() + r0 * n_classes * 4, _native.stream_of(X))
+                return out
+        cls = self.value[self.leaves(X)].round().long().clamp(0, n_classes - 1)
+        out = torch.zeros(n, n_classes, dtype=torch.int32, device=cls.device)
+        return out.scatter_add_(1, cls, torch.ones_like(cls, dtype=torch.int32))
 
     @torch.no_grad()
     def leaves(self, X: torch.Tensor) -> torch.Tensor:
@@ -259,19 +297,18 @@ class TreeScorer:
     def score(self, table) -> np.ndarray:
         return self.score_bags(self.input_matrix(table)).mean(1)
 
-    def class_votes(self, table, n_classes: int, chunk: int = 1 << 16) -> np.ndarray:
+    @torch.no_grad()
+    def class_votes(self, table, n_classes: int, chunk: int | None = None) -> np.ndarray:
         """Native multi-class forests (classification leaves carry a class value): per row the
         fraction of trees voting for each class, averaged over bags -> [N, n_classes]
         (``computeClassificationScore`` returns every tree's class; the caller votes)."""
         X = self.input_matrix(table)
-        out = np.zeros((X.shape[0], n_classes))
+        chunk = chunk or ((1 << 20) if X.is_cuda else (1 << 16))
+        out = torch.zeros(X.shape[0], n_classes, dtype=torch.float64, device=X.device)
         for e in self.ens:
             for i in range(0, X.shape[0], chunk):
-                lv = e.value[e.leaves(X[i: i + chunk])].round().long().clamp(0, n_classes - 1)
-                cnt = torch.zeros(lv.shape[0], n_classes, dtype=torch.float64, device=lv.device)
-                cnt.scatter_add_(1, lv, torch.ones_like(lv, dtype=torch.float64))
-                out[i: i + chunk] += (cnt / max(lv.shape[1], 1)).cpu().numpy()
-        return out / max(len(self.ens), 1)
+                out[i: i + chunk] += e.votes(X[i: i + chunk], n_classes).double() / max(int(e.roots.numel()), 1)
+        return out.cpu().numpy() / max(len(self.ens), 1)
 
     @torch.no_grad()
     def encode(self, table, depth: int | None = None) -> np.ndarray:
