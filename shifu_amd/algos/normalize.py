@@ -364,7 +364,8 @@ def normalize_table_gpu(mc, ccs, table, columns=None, norm_type: str | None = No
 
 
 def tree_bin_codes_gpu(ccs, table, columns, device="cuda"):
-    """HIP CleanedData codes (uint8, nbins <= 256)."""
+    """HIP CleanedData codes: the uint8 kernel when every feature has at most 256 bins, the int16
+    one up to 16384 (None above: the wide-feature trainer's own limit)."""
     import torch
     from ..ops import stats_ops
     nbins, is_cat, ncat, bounds = [], [], [], []
@@ -375,11 +376,12 @@ def tree_bin_codes_gpu(ccs, table, columns, device="cuda"):
         else:
             bb = cc.bin_boundary or [float("-inf")]
             nbins.append(max(1, len(bb))); is_cat.append(0); ncat.append(0); bounds.append(bb)
-    if max(nbins, default=1) > 256:
+    if max(nbins, default=1) > stats_ops.WIDE_NB:
         return None
     dev = torch.device(device)
     vals = _raw_matrix_dev(columns, table, dev)
-    out = torch.zeros(table.n, max(1, len(columns)), dtype=torch.uint8, device=dev)
+    out = torch.zeros(table.n, max(1, len(columns)), device=dev,
+                      dtype=torch.uint8 if max(nbins, default=1) <= 256 else torch.int16)
     stats_ops.bin_codes(vals, is_cat, bounds, ncat, out)
     return out.cpu().numpy().astype(np.int32), np.array(nbins, np.int32), np.array(is_cat, np.uint8)
 
@@ -390,7 +392,8 @@ class NormPlan:
     columns' kernel specs (device tensors), the host-side one-hot columns, and the tree-code spec.
     ``run(table)`` normalizes one chunk: on the GPU one ``norm_codes`` launch reads the raw values
     once and writes the fp32 rows and/or the bf16 GEMM-ready rows (``kpad`` wide, bias column =
-    1 at ``width``) and/or the uint8 CleanedData codes; on the CPU the numpy oracle does the same."""
+    1 at ``width``) and/or the CleanedData codes (uint8, or int16 when a feature has 257-16384
+    bins); on the CPU the numpy oracle does the same."""
 
     def __init__(self, mc, ccs, cols, norm_type: str | None = None, want_x: bool = True,
                  want_codes: bool = False, x_dtype: str = "float32", device=None, pinned_out: int = 0):
@@ -536,14 +539,18 @@ class NormPlan:
             return out
         import torch
         from ..ops import _native as nat
-        need_codes = self.want_codes and self.code_dtype == np.uint8
+        from ..ops.stats_ops import WIDE_NB
+        need_codes = self.want_codes and self.nbins.max(initial=1) <= WIDE_NB
+        i16 = self.code_dtype == np.int16
+        kern = "shifu_norm_codes_i16" if need_codes and i16 else "shifu_norm_codes"
         dev_cols = self.gpu_cols if not need_codes else self.cols
         vals = _raw_matrix_dev(dev_cols, table, self.dev) if dev_cols else None
         ds = self._device_specs()
         outf = self._buf("f", (n, max(self.width, 1)), torch.float32) if (self.want_x and not bf16) else None
         outb = self._buf("b", (n, self.kpad), torch.bfloat16,
                          init=lambda b: b[:, self.width].fill_(1.0)) if bf16 else None
-        codes = self._buf("c", (n, max(1, len(self.cols))), torch.uint8) if need_codes else None
+        codes = self._buf("c", (n, max(1, len(self.cols))), torch.int16 if i16 else torch.uint8) \
+            if need_codes else None
         if vals is not None and n:
             if need_codes and len(self.gpu_cols) != len(self.cols):
                 # one-hot columns present: the width-1 specs index the gpu columns only -> two passes
@@ -552,13 +559,13 @@ class NormPlan:
                                   ds["bounds"], ds["tables"], None, None, outf, 0 if outf is None else outf.stride(0),
                                   outb, 0 if outb is None else outb.stride(0), None, 0, nat.stream_of(sub)) \
                     if self.gpu_cols and (outf is not None or outb is not None) else 0
-                rc2 = nat.call_hip("shifu_norm_codes", vals, vals.stride(0), n, len(self.cols), None, None, None, None,
+                rc2 = nat.call_hip(kern, vals, vals.stride(0), n, len(self.cols), None, None, None, None,
                                    ds["cip"], ds["cbounds"], None, 0, None, 0, codes, codes.stride(0),
                                    nat.stream_of(vals))
                 rc = rc or rc2
             else:
                 want_v = outf is not None or outb is not None
-                rc = nat.call_hip("shifu_norm_codes", vals, vals.stride(0), n, vals.shape[0],
+                rc = nat.call_hip(kern, vals, vals.stride(0), n, vals.shape[0],
                                   ds["ip"] if want_v else None, ds["dp"] if want_v else None, ds["bounds"], ds["tables"],
                                   ds["cip"] if need_codes else None, ds["cbounds"] if need_codes else None,
                                   outf, 0 if outf is None else outf.stride(0), outb,

@@ -106,9 +106,13 @@ HIP_SIGNATURES = {
     "shifu_gbdt_split_mc": "pppp" "i" "ppp" "pp" "iiii" "ddd" "pp" "s",
     # stats_kernels.hip
     "shifu_column_stats": "plppli" "ppii" "dd" "pipiip" "s",
+    "shifu_column_stats_cols": "plppli" "ppii" "dd" "pipiip" "p" "s",
+    "shifu_column_stats_wide": "plpl" "ppii" "idd" "pipiip" "s",
     "shifu_normalize": "plli" "pppp" "pl" "s",
     "shifu_bin_codes": "plli" "pp" "pl" "s",
+    "shifu_bin_codes_i16": "plli" "pp" "pl" "s",
     "shifu_norm_codes": "plli" "pppp" "pp" "pl" "pl" "pl" "s",
+    "shifu_norm_codes_i16": "plli" "pppp" "pp" "pl" "pl" "pl" "s",
     "shifu_onehot": "plli" "pp" "pl" "pl" "s",
     "shifu_lr_grad": "plli" "i" "ppp" "pp" "i" "s",
     "shifu_sensitivity": "plpl" "pp" "f" "p" "l" "iiiii" "p" "s",

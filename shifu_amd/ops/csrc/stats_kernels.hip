@@ -14,7 +14,8 @@
 // Design notes:
 //   * column-major raw values [F][ldv] fp64 (one column = one contiguous stream, exact double
 //     comparisons against double bin boundaries, same as the Java code); boundaries are staged in
-//     LDS per block and searched branch-free.
+//     LDS per block and searched branch-free (up to 1024 per column; 1025-16384: every 16th in
+//     LDS, the rest from L2, column_stats_wide_kernel).
 //   * histograms: LDS-privatised integer counters (ds_add_u32 for counts, ds_add_u64 for fixed-
 //     point weights - integer LDS atomics are ~17x faster than ds_add_f32 on gfx950, see
 //     profiles/microbench_lds_atomics.txt) flushed once per block; moments are fp64 wave/block
@@ -56,6 +57,8 @@ struct StatsArgs {
   const unsigned int* posbits;               // binary: bit r = (y[r] > 0.5), packed (1 bit per row)
   int max_nb;                                // max boundaries over the batch (sizes the LDS carve)
   int priv;                                  // per-thread private counters (unit_w, few bins)
+  const int* cols;                           // nullable: block x -> column cols[x] of vals / part (boff and
+                                             // hist stay indexed by x): the narrow columns of a mixed batch
 };
 
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
@@ -91,8 +94,9 @@ __global__ void __launch_bounds__(256) column_stats_kernel(StatsArgs a) {
   unsigned int* priv = (unsigned int*)tail;                       // [2 m1][256]
   unsigned long long* wp = (unsigned long long*)tail;             // [m1]
   unsigned long long* wn = wp + m1;
-  const int f = blockIdx.x, chunk = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
-  const int b0 = a.boff[f], nb = a.boff[f + 1] - b0;
+  const int slot = blockIdx.x, chunk = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+  const int f = a.cols ? a.cols[slot] : slot;
+  const int b0 = a.boff[slot], nb = a.boff[slot + 1] - b0;
   const bool private_cnt = a.priv;
   for (int i = tid; i < nb; i += 256) sb[i] = a.bounds[b0 + i];
   for (int i = tid; i <= nb; i += 256) {
@@ -164,7 +168,7 @@ __global__ void __launch_bounds__(256) column_stats_kernel(StatsArgs a) {
     if (tid == 7) acc = 0.0;
     a.part[((long)f * a.nchunks + chunk) * 8 + tid] = acc;
   }
-  unsigned long long* h = a.hist + (long)f * a.hstride * 4;
+  unsigned long long* h = a.hist + (long)slot * a.hstride * 4;
   const unsigned long long unit_q = (unsigned long long)__double2ll_rn(a.wscale);
   for (int i = tid; i <= nb; i += 256) {
     const unsigned long long wpi = a.unit_w ? (unsigned long long)cp[i] * unit_q : wp[i];
@@ -173,6 +177,148 @@ __global__ void __launch_bounds__(256) column_stats_kernel(StatsArgs a) {
     if (cn[i]) atomicAdd(&h[i * 4 + 1], (unsigned long long)cn[i]);
     if (wpi) atomicAdd(&h[i * 4 + 2], wpi);
     if (wni) atomicAdd(&h[i * 4 + 3], wni);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// K1+K2 wide: columns with 1025-16384 boundaries (high-cardinality numerics binned finely).
+// 16384 boundaries alone are 128 KiB, so nothing of column_stats_kernel's layout fits; instead:
+//   * two-level search.  Every 16th boundary (<= 1024 doubles, 8 KiB) is staged in LDS and searched
+//     branch-free; the row then finishes over the 16 boundaries of ONE 128-byte line of global
+//     memory (8 independent 16-byte loads, L2 resident: a column's boundaries are read by every
+//     row of every block of that column).  The host pads each column's boundaries with NaN to a
+//     multiple of 16 at a 16-double aligned offset, so the line needs no bounds test and a pad
+//     never counts (NaN <= v is false).  The result is the count of boundaries <= v, as bin_search.
+//   * the bin axis is tiled over blockIdx.z: a block counts the rows whose bin falls in its tile
+//     and skips the others; tile z = 0 also owns the (column, chunk) moments.
+//       unit weights : u32 (pos, neg) per bin, 8 B -> one tile of all 16385 bins:
+//                      8 KiB index + 128 KiB counters = 136 KiB
+//       real weights : + u64 fixed-point (pos, neg), 24 B -> tiles of 6144 bins, <= 3 tiles:
+//                      8 KiB index + 144 KiB counters = 152 KiB
+//     Both stay under WIDE_LDS = 152 KiB of the CU's 160 KiB (the static moment scratch is 256 B).
+//   * skew: where the tile leaves room (fewer bins than the limit) the counters are replicated up
+//     to 8 times and lane l adds into copy l & (copies - 1), so a hot bin (missing, zero) spreads
+//     a wave's atomics over `copies` addresses; the flush sums the copies.
+// Flush: integer global atomics into hist[slot][hstride][4], as the narrow kernel.
+// ---------------------------------------------------------------------------------------------
+constexpr int WIDE_NB = 16384;                // max boundaries per column
+constexpr int WG = 16;                        // boundaries per coarse entry = one 128-byte line
+constexpr long WIDE_LDS = 152 * 1024;
+constexpr int WIDE_TILE_W = 6144;             // bins per tile with real weights
+
+struct WideStatsArgs {
+  const double* vals; long ldv; const double* w; long n;
+  const double* wb;                          // padded boundaries (see above)
+  const int* meta;                           // [Fw][4]: column of vals / part, offset into wb, nb, 0
+  int binary; double wscale; double num_thr;
+  unsigned long long* hist; int hstride;     // [Fw][hstride][4] by slot
+  double* part; int nchunks; long rows_per_chunk;   // [F][nchunks][8] by column
+  int unit_w; const unsigned int* posbits;
+  int max_nb;                                // most boundaries over the slots (sizes the coarse index)
+  int tile, copies;                          // bins per tile; counter copies (power of two)
+};
+
+__host__ __device__ inline long wide_lds_bytes(int max_nb, int tile, int copies, int unit_w) {
+  return (long)((max_nb + WG - 1) / WG) * 8 + (long)copies * tile * (unit_w ? 8 : 24);
+}
+
+__global__ void __launch_bounds__(256) column_stats_wide_kernel(WideStatsArgs a) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  __shared__ double red[4][8];
+  const int slot = blockIdx.x, chunk = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+  const int f = a.meta[slot * 4], nb = a.meta[slot * 4 + 2];
+  const int t0 = blockIdx.z * a.tile;
+  if (nb > a.max_nb || t0 > nb) return;       // block-uniform: this column has no bins in the tile
+  const double* __restrict__ b = a.wb + a.meta[slot * 4 + 1];
+  const int tn = min(a.tile, nb + 1 - t0);    // bins of this tile (the missing bin nb is the last)
+  const int nc = (nb + WG - 1) / WG;
+  const long cstride = 2L * a.tile;           // one copy: pos [tile], neg [tile]
+  double* sc = (double*)smem;
+  unsigned long long* wq = (unsigned long long*)(sc + (a.max_nb + WG - 1) / WG);
+  unsigned int* cnt = (unsigned int*)(wq + (a.unit_w ? 0 : a.copies * cstride));
+  for (int i = tid; i < nc; i += 256) sc[i] = b[(long)i * WG];
+  for (long i = tid; i < a.copies * cstride; i += 256) {
+    cnt[i] = 0u;
+    if (!a.unit_w) wq[i] = 0ull;
+  }
+  __syncthreads();
+  unsigned int* mc = cnt + (lane & (a.copies - 1)) * cstride;
+  unsigned long long* mw = wq + (lane & (a.copies - 1)) * cstride;
+  const bool first = blockIdx.z == 0;
+  const long r0 = (long)chunk * a.rows_per_chunk;
+  const long r1 = min(a.n, r0 + a.rows_per_chunk);
+  const double* col = a.vals + (long)f * a.ldv;
+  double n1 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, mn = INFINITY, mx = -INFINITY;
+  for_rows<4>(col, r0, r1, 256, [&](long r, double v) {
+    if (v > a.num_thr) v = NAN;               // numericalValueThreshold -> invalid
+    int bin = nb;                             // missing bin
+    if (v == v) {
+      int pos = 0;                            // coarse entries <= v
+#pragma unroll
+      for (int step = 1024; step > 0; step >>= 1) {
+        const int t = pos + step;
+        const double c = sc[min(t, nc) - 1];
+        pos = (t <= nc && c <= v) ? t : pos;
+      }
+      // pos = 0: b[0] > v, and line 0 counts nothing
+      const int g = max(pos - 1, 0);
+      const double2* __restrict__ line = (const double2*)(b + (long)g * WG);
+      int m = 0;
+#pragma unroll
+      for (int k = 0; k < WG / 2; ++k) {
+        const double2 x = line[k];
+        m += (x.x <= v ? 1 : 0) + (x.y <= v ? 1 : 0);
+      }
+      const int idx = g * WG + m - 1;
+      bin = idx < 0 ? 0 : (idx > nb - 1 ? nb - 1 : idx);
+      if (first && isfinite(v)) {
+        const double v2 = v * v;
+        n1 += 1.0; s1 += v; s2 += v2; s3 += v2 * v; s4 += v2 * v2;
+        mn = fmin(mn, v); mx = fmax(mx, v);
+      }
+    }
+    const int tb = bin - t0;
+    if ((unsigned)tb >= (unsigned)tn) return;
+    const bool pos_row = !a.binary || ((a.posbits[r >> 5] >> (r & 31)) & 1u);
+    const int k = pos_row ? tb : a.tile + tb;
+    atomicAdd(&mc[k], 1u);
+    if (!a.unit_w) atomicAdd(&mw[k], (unsigned long long)__double2ll_rn(a.w[r] * a.wscale));
+  });
+  // moments: wave then block reduction (tile 0 writes them)
+  n1 = wave_sum_d(n1); s1 = wave_sum_d(s1); s2 = wave_sum_d(s2); s3 = wave_sum_d(s3); s4 = wave_sum_d(s4);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    mn = fmin(mn, __shfl_xor(mn, o, 64));
+    mx = fmax(mx, __shfl_xor(mx, o, 64));
+  }
+  const int wid = tid >> 6;
+  if (lane == 0) {
+    red[wid][0] = n1; red[wid][1] = s1; red[wid][2] = s2; red[wid][3] = s3; red[wid][4] = s4;
+    red[wid][5] = mn; red[wid][6] = mx; red[wid][7] = 0.0;
+  }
+  __syncthreads();                            // red complete, and every LDS atomic of the block done
+  if (first && tid < 8) {
+    double acc = red[0][tid];
+    for (int k = 1; k < 4; ++k) {
+      const double v = red[k][tid];
+      acc = tid == 5 ? fmin(acc, v) : (tid == 6 ? fmax(acc, v) : acc + v);
+    }
+    a.part[((long)f * a.nchunks + chunk) * 8 + tid] = acc;
+  }
+  unsigned long long* h = a.hist + ((long)slot * a.hstride + t0) * 4;
+  const unsigned long long unit_q = (unsigned long long)__double2ll_rn(a.wscale);
+  for (int i = tid; i < tn; i += 256) {
+    unsigned long long cp = 0, cn = 0, wp = 0, wn = 0;
+    for (int c = 0; c < a.copies; ++c) {
+      cp += cnt[c * cstride + i];
+      cn += cnt[c * cstride + a.tile + i];
+      if (!a.unit_w) { wp += wq[c * cstride + i]; wn += wq[c * cstride + a.tile + i]; }
+    }
+    if (a.unit_w) { wp = cp * unit_q; wn = cn * unit_q; }
+    if (cp) atomicAdd(&h[i * 4 + 0], cp);
+    if (cn) atomicAdd(&h[i * 4 + 1], cn);
+    if (wp) atomicAdd(&h[i * 4 + 2], wp);
+    if (wn) atomicAdd(&h[i * 4 + 3], wn);
   }
 }
 
@@ -253,33 +399,41 @@ __global__ void __launch_bounds__(256) normalize_kernel(NormArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// K1': tree bin codes (CleanedData): numeric missing -> bin of 0.0, categorical missing -> ncat
+// K1': tree bin codes (CleanedData): numeric missing -> bin of 0.0, categorical missing -> ncat.
+// CT = uint8_t (every feature <= 256 bins) or int16_t (up to 16384 bins: the numeric search runs
+// over up to 16384 boundaries in global memory, categorical codes are index clamps).  The LDS
+// transpose tile is typed and padded per CT: rows of 17 (uint8) / 33 (int16) 32-bit words, both
+// odd, so the transposed read is bank-conflict free.
 // ---------------------------------------------------------------------------------------------
+template <typename CT> constexpr int code_tile_ld() { return 64 + 4 / (int)sizeof(CT); }
+
+template <typename CT>
 struct CodeArgs {
   const double* vals; long ldv; long n; int F;
   const int* ip;        // [F][4]: is_cat, bnd_off, nbnd, ncat
   const double* bounds;
-  uint8_t* out; long ldo;
+  CT* out; long ldo;
 };
 
-__global__ void __launch_bounds__(256) bin_codes_kernel(CodeArgs a) {
-  __shared__ uint8_t tile[64][68];
+template <typename CT>
+__global__ void __launch_bounds__(256) bin_codes_kernel(CodeArgs<CT> a) {
+  __shared__ CT tile[64][code_tile_ld<CT>()];
   const long r0 = (long)blockIdx.x * 64;
   const int f0 = blockIdx.y * 64;
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   for (int k = ty; k < 64; k += 4) {
     const int f = f0 + k;
     const long r = r0 + tx;
-    uint8_t c = 0;
+    CT c = 0;
     if (f < a.F && r < a.n) {
       const int* ip = a.ip + f * 4;
       double v = a.vals[(long)f * a.ldv + r];
       if (ip[0]) {
         int idx = (v != v || v < 0) ? -1 : (int)v;
-        c = (uint8_t)((idx < 0 || idx >= ip[3]) ? ip[3] : idx);
+        c = (CT)((idx < 0 || idx >= ip[3]) ? ip[3] : idx);
       } else {
         if (v != v) v = 0.0;                 // DTWorker.getFloatValue: missing -> 0f
-        c = (uint8_t)bin_search(a.bounds + ip[1], ip[2], v);
+        c = (CT)bin_search(a.bounds + ip[1], ip[2], v);
       }
     }
     tile[k][tx] = c;
@@ -296,16 +450,17 @@ __global__ void __launch_bounds__(256) bin_codes_kernel(CodeArgs a) {
 // K5 fused (streamed `norm`): one read of a chunk's raw values -> every NormalizedData /
 // CleanedData output of the chunk in the same pass: fp32 rows (the NormalizedData cache),
 // bf16 GEMM-ready rows (the MLP's padded layout: the caller's buffer holds the bias column and
-// the zero padding, the kernel fills the value columns) and uint8 tree codes.  Column-major fp64
+// the zero padding, the kernel fills the value columns) and uint8 / int16 tree codes (CT).  Column-major fp64
 // in, row-major out through one LDS transpose tile per output; each output is optional.
 // ---------------------------------------------------------------------------------------------
+template <typename CT>
 struct NormCodesArgs {
   const double* vals; long ldv; long n; int F;
   const int* ip; const double* dp; const double* bounds; const double* tables;   // as NormArgs
   const int* cip; const double* cbounds;   // codes: [F][4] is_cat, bnd_off, nbnd, ncat (nullable)
   float* outf; long ldf;                   // [n][ldf] fp32 at out_col (nullable)
   bf16_t* outb; long ldb;                  // [n][ldb] bf16 at out_col (nullable)
-  uint8_t* codes; long ldc;                // [n][ldc] uint8 at column f (nullable)
+  CT* codes; long ldc;                     // [n][ldc] codes at column f (nullable)
 };
 
 __device__ __forceinline__ double norm_value(const int* ip, const double* dp, const double* bounds,
@@ -338,9 +493,10 @@ __device__ __forceinline__ double norm_value(const int* ip, const double* dp, co
   }
 }
 
-__global__ void __launch_bounds__(256) norm_codes_kernel(NormCodesArgs a) {
+template <typename CT>
+__global__ void __launch_bounds__(256) norm_codes_kernel(NormCodesArgs<CT> a) {
   __shared__ float tile[64][65];
-  __shared__ uint8_t ctile[64][68];
+  __shared__ CT ctile[64][code_tile_ld<CT>()];
   const long r0 = (long)blockIdx.x * 64;
   const int f0 = blockIdx.y * 64;
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;   // 64 x 4
@@ -348,7 +504,7 @@ __global__ void __launch_bounds__(256) norm_codes_kernel(NormCodesArgs a) {
     const int f = f0 + k;
     const long r = r0 + tx;
     float res = 0.f;
-    uint8_t c = 0;
+    CT c = 0;
     if (f < a.F && r < a.n) {
       double v = a.vals[(long)f * a.ldv + r];          // coalesced: consecutive rows of column f
       if (a.outf || a.outb) res = (float)norm_value(a.ip + f * 8, a.dp + f * 8, a.bounds, a.tables, v);
@@ -356,10 +512,10 @@ __global__ void __launch_bounds__(256) norm_codes_kernel(NormCodesArgs a) {
         const int* cp = a.cip + f * 4;
         if (cp[0]) {
           const int idx = (v != v || v < 0) ? -1 : (int)v;
-          c = (uint8_t)((idx < 0 || idx >= cp[3]) ? cp[3] : idx);
+          c = (CT)((idx < 0 || idx >= cp[3]) ? cp[3] : idx);
         } else {
           if (v != v) v = 0.0;                         // DTWorker.getFloatValue: missing -> 0f
-          c = (uint8_t)bin_search(a.cbounds + cp[1], cp[2], v);
+          c = (CT)bin_search(a.cbounds + cp[1], cp[2], v);
         }
       }
     }
@@ -605,18 +761,63 @@ __global__ void __launch_bounds__(256) sensitivity_kernel(SensArgs a) {
 // ---------------------------------------------------------------------------------------------
 // C API
 // ---------------------------------------------------------------------------------------------
-SHIFU_API int shifu_column_stats(const double* vals, long ldv, const float* y, const double* w, long n, int F,
-                                 const double* bounds, const int* boff, int max_nb, int binary, double wscale,
-                                 double num_thr, void* hist, int hstride, double* part, int nchunks, int unit_w,
-                                 const unsigned int* posbits, hipStream_t stream) {
+static int launch_column_stats(const double* vals, long ldv, const float* y, const double* w, long n, int F,
+                               const double* bounds, const int* boff, int max_nb, int binary, double wscale,
+                               double num_thr, void* hist, int hstride, double* part, int nchunks, int unit_w,
+                               const unsigned int* posbits, const int* cols, hipStream_t stream) {
   if (binary && !posbits) return -1;
   if (max_nb > MAXB || hstride < max_nb + 1 || nchunks <= 0 || nchunks > 65535 || F <= 0) return -1;
   const int priv = unit_w && 2 * (max_nb + 1) <= PRIV_KEYS;
   StatsArgs a{vals, ldv, y, w, n, bounds, boff, binary, wscale, num_thr, (unsigned long long*)hist, hstride,
-              part, nchunks, (n + nchunks - 1) / nchunks, unit_w, posbits, max_nb, priv};
+              part, nchunks, (n + nchunks - 1) / nchunks, unit_w, posbits, max_nb, priv, cols};
   const long lds = cs_lds_bytes(max_nb, priv, unit_w);
   if (lds > 150 * 1024) return -1;
   hipLaunchKernelGGL(column_stats_kernel, dim3(F, nchunks), dim3(256), (unsigned)lds, stream, a);
+  CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+SHIFU_API int shifu_column_stats(const double* vals, long ldv, const float* y, const double* w, long n, int F,
+                                 const double* bounds, const int* boff, int max_nb, int binary, double wscale,
+                                 double num_thr, void* hist, int hstride, double* part, int nchunks, int unit_w,
+                                 const unsigned int* posbits, hipStream_t stream) {
+  return launch_column_stats(vals, ldv, y, w, n, F, bounds, boff, max_nb, binary, wscale, num_thr, hist, hstride,
+                             part, nchunks, unit_w, posbits, nullptr, stream);
+}
+
+// The F narrow columns cols[0..F) of a batch that also holds wide ones: boff / hist are indexed by
+// the position in cols, vals / part by the column.
+SHIFU_API int shifu_column_stats_cols(const double* vals, long ldv, const float* y, const double* w, long n, int F,
+                                      const double* bounds, const int* boff, int max_nb, int binary, double wscale,
+                                      double num_thr, void* hist, int hstride, double* part, int nchunks,
+                                      int unit_w, const unsigned int* posbits, const int* cols,
+                                      hipStream_t stream) {
+  if (!cols) return -1;
+  return launch_column_stats(vals, ldv, y, w, n, F, bounds, boff, max_nb, binary, wscale, num_thr, hist, hstride,
+                             part, nchunks, unit_w, posbits, cols, stream);
+}
+
+// The Fw wide columns (1025-16384 boundaries) of a batch.  wb / meta: see column_stats_wide_kernel;
+// every nb in meta is <= max_nb.  hist [Fw][hstride][4] by position in meta, part by column.
+SHIFU_API int shifu_column_stats_wide(const double* vals, long ldv, const double* w, long n, const double* wb,
+                                      const int* meta, int Fw, int max_nb, int binary, double wscale,
+                                      double num_thr, void* hist, int hstride, double* part, int nchunks,
+                                      int unit_w, const unsigned int* posbits, hipStream_t stream) {
+  if (binary && !posbits) return -1;
+  if (!unit_w && !w) return -1;
+  if (max_nb <= MAXB || max_nb > WIDE_NB || hstride < max_nb + 1 || nchunks <= 0 || nchunks > 65535 || Fw <= 0)
+    return -1;
+  const int tile = (unit_w || max_nb + 1 < WIDE_TILE_W) ? max_nb + 1 : WIDE_TILE_W;
+  int copies = 8;
+  while (copies > 1 && wide_lds_bytes(max_nb, tile, copies, unit_w) > WIDE_LDS) copies >>= 1;
+  const long lds = wide_lds_bytes(max_nb, tile, copies, unit_w);
+  if (lds > WIDE_LDS) return -1;
+  const int ntiles = (max_nb + 1 + tile - 1) / tile;
+  WideStatsArgs a{vals, ldv, w, n, wb, meta, binary, wscale, num_thr, (unsigned long long*)hist, hstride,
+                  part, nchunks, (n + nchunks - 1) / nchunks, unit_w, posbits, max_nb, tile, copies};
+  CHECK_HIP(hipFuncSetAttribute((const void*)column_stats_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds));
+  hipLaunchKernelGGL(column_stats_wide_kernel, dim3(Fw, nchunks, ntiles), dim3(256), (unsigned)lds, stream, a);
   CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -630,27 +831,57 @@ SHIFU_API int shifu_normalize(const double* vals, long ldv, long n, int F, const
   return 0;
 }
 
+template <typename CT>
+static int launch_norm_codes(const double* vals, long ldv, long n, int F, const int* ip, const double* dp,
+                             const double* bounds, const double* tables, const int* cip, const double* cbounds,
+                             float* outf, long ldf, void* outb, long ldb, void* codes, long ldc,
+                             hipStream_t stream) {
+  if (n <= 0 || F <= 0) return 0;
+  if ((outf || outb) && (!ip || !dp)) return -1;
+  if (codes && (!cip || !cbounds || ldc < F)) return -1;
+  NormCodesArgs<CT> a{vals, ldv, n, F, ip, dp, bounds, tables, cip, cbounds, outf, ldf, (bf16_t*)outb, ldb,
+                      (CT*)codes, ldc};
+  hipLaunchKernelGGL(norm_codes_kernel<CT>, dim3((n + 63) / 64, (F + 63) / 64), dim3(256), 0, stream, a);
+  CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 SHIFU_API int shifu_norm_codes(const double* vals, long ldv, long n, int F, const int* ip, const double* dp,
                                const double* bounds, const double* tables, const int* cip, const double* cbounds,
                                float* outf, long ldf, void* outb, long ldb, void* codes, long ldc,
                                hipStream_t stream) {
+  return launch_norm_codes<uint8_t>(vals, ldv, n, F, ip, dp, bounds, tables, cip, cbounds, outf, ldf, outb, ldb,
+                                    codes, ldc, stream);
+}
+
+// int16 codes [n][ldc] (ldc in elements): features of up to 16384 bins
+SHIFU_API int shifu_norm_codes_i16(const double* vals, long ldv, long n, int F, const int* ip, const double* dp,
+                                   const double* bounds, const double* tables, const int* cip,
+                                   const double* cbounds, float* outf, long ldf, void* outb, long ldb, void* codes,
+                                   long ldc, hipStream_t stream) {
+  return launch_norm_codes<int16_t>(vals, ldv, n, F, ip, dp, bounds, tables, cip, cbounds, outf, ldf, outb, ldb,
+                                    codes, ldc, stream);
+}
+
+template <typename CT>
+static int launch_bin_codes(const double* vals, long ldv, long n, int F, const int* ip, const double* bounds,
+                            void* out, long ldo, hipStream_t stream) {
   if (n <= 0 || F <= 0) return 0;
-  if ((outf || outb) && (!ip || !dp)) return -1;
-  if (codes && (!cip || !cbounds || ldc < F)) return -1;
-  NormCodesArgs a{vals, ldv, n, F, ip, dp, bounds, tables, cip, cbounds, outf, ldf, (bf16_t*)outb, ldb,
-                  (uint8_t*)codes, ldc};
-  hipLaunchKernelGGL(norm_codes_kernel, dim3((n + 63) / 64, (F + 63) / 64), dim3(256), 0, stream, a);
+  if (ldo < F) return -1;
+  CodeArgs<CT> a{vals, ldv, n, F, ip, bounds, (CT*)out, ldo};
+  hipLaunchKernelGGL(bin_codes_kernel<CT>, dim3((n + 63) / 64, (F + 63) / 64), dim3(256), 0, stream, a);
   CHECK_HIP(hipGetLastError());
   return 0;
 }
 
 SHIFU_API int shifu_bin_codes(const double* vals, long ldv, long n, int F, const int* ip, const double* bounds,
                               void* out, long ldo, hipStream_t stream) {
-  if (n <= 0 || F <= 0) return 0;
-  CodeArgs a{vals, ldv, n, F, ip, bounds, (uint8_t*)out, ldo};
-  hipLaunchKernelGGL(bin_codes_kernel, dim3((n + 63) / 64, (F + 63) / 64), dim3(256), 0, stream, a);
-  CHECK_HIP(hipGetLastError());
-  return 0;
+  return launch_bin_codes<uint8_t>(vals, ldv, n, F, ip, bounds, out, ldo, stream);
+}
+
+SHIFU_API int shifu_bin_codes_i16(const double* vals, long ldv, long n, int F, const int* ip, const double* bounds,
+                                  void* out, long ldo, hipStream_t stream) {
+  return launch_bin_codes<int16_t>(vals, ldv, n, F, ip, bounds, out, ldo, stream);
 }
 
 template <typename T>

@@ -52,31 +52,103 @@ def pack_bounds(bounds_list):
     return np.asarray(flat if flat else [0.0], np.float64), np.asarray(offs, np.int32)
 
 
+NARROW_NB, WIDE_NB = 1024, 16384     # most boundaries of column_stats_kernel / column_stats_wide_kernel
+
+
+def _stats_plan(bounds_list, dev):
+    """Packed boundaries of one column batch on the device, split by kernel: columns of at most
+    NARROW_NB boundaries go to ``column_stats_kernel`` (one launch sized by the largest NARROW
+    count, so a wide column costs the others neither their private counters nor LDS), columns of
+    up to WIDE_NB boundaries to ``column_stats_wide_kernel``."""
+    bflat, boff = pack_bounds(bounds_list)
+    lens = np.diff(boff)
+    F = len(lens)
+    max_nb = int(lens.max()) if F else 1
+    if max_nb > WIDE_NB:
+        raise ValueError(f"column_stats: more than {WIDE_NB} bin boundaries per column")
+    wide = np.flatnonzero(lens > NARROW_NB)
+    plan = dict(F=F, boff=boff, hstride=max_nb + 1, wide=wide, narrow=None, Fn=F, n_nb=max_nb, n_cols=None)
+    if not len(wide):
+        plan.update(n_bt=_dev_tensor(bflat, torch.float64, dev), n_ot=_dev_tensor(boff, torch.int32, dev))
+        return plan
+    narrow = np.flatnonzero(lens <= NARROW_NB)
+    plan.update(narrow=narrow, Fn=len(narrow))
+    if len(narrow):
+        nflat, noff = pack_bounds([bflat[boff[f]: boff[f + 1]] for f in narrow])
+        plan.update(n_nb=int(np.diff(noff).max()), n_bt=_dev_tensor(nflat, torch.float64, dev),
+                    n_ot=_dev_tensor(noff, torch.int32, dev), n_cols=_dev_tensor(narrow, torch.int32, dev))
+    # the wide kernel reads a column's boundaries as whole 128-byte lines of 16: every column starts
+    # at a multiple of 16 doubles and is padded to one with NaN (never <= a value)
+    meta, rows, off = np.zeros((len(wide), 4), np.int32), [], 0
+    for k, f in enumerate(wide):
+        nb = int(lens[f])
+        meta[k] = [f, off, nb, 0]
+        rows += [bflat[boff[f]: boff[f + 1]], np.full(-nb % 16, np.nan)]
+        off += nb + -nb % 16
+    plan.update(w_nb=int(lens[wide].max()), w_bt=_dev_tensor(np.concatenate(rows), torch.float64, dev),
+                w_meta=_dev_tensor(meta, torch.int32, dev))
+    return plan
+
+
+def _stats_launch(plan, vals, y, w, N, binary, wscale, num_thr, nchunks, unit_w, posbits):
+    """K1+K2 of one batch -> ([hist of the narrow columns [Fn * (n_nb + 1) * 4], hist of the wide
+    columns [Fw * (w_nb + 1) * 4]] (whichever exist), moment partials [F * nchunks * 8])."""
+    dev, st = vals.device, nat.stream_of(vals)
+    part = torch.zeros(plan["F"] * nchunks * 8, dtype=torch.float64, device=dev)
+    hists = []
+    Fw = len(plan["wide"])
+    if plan["Fn"] or not Fw:
+        hs = plan["n_nb"] + 1
+        hist = torch.zeros(plan["Fn"] * hs * 4, dtype=torch.int64, device=dev)
+        args = (vals, vals.stride(0), y, w, N, plan["Fn"], plan["n_bt"], plan["n_ot"], plan["n_nb"], int(binary),
+                wscale, float(num_thr), hist, hs, part, nchunks, int(unit_w), posbits)
+        if plan["n_cols"] is None:
+            rc = nat.call_hip("shifu_column_stats", *args, st)
+        else:
+            rc = nat.call_hip("shifu_column_stats_cols", *args, plan["n_cols"], st)
+        if rc:
+            raise RuntimeError(f"shifu_column_stats failed rc={rc}")
+        hists.append(hist)
+    if Fw:
+        hs = plan["w_nb"] + 1
+        hist = torch.zeros(Fw * hs * 4, dtype=torch.int64, device=dev)
+        rc = nat.call_hip("shifu_column_stats_wide", vals, vals.stride(0), w, N, plan["w_bt"], plan["w_meta"], Fw,
+                          plan["w_nb"], int(binary), wscale, float(num_thr), hist, hs, part, nchunks, int(unit_w),
+                          posbits, st)
+        if rc:
+            raise RuntimeError(f"shifu_column_stats_wide failed rc={rc}")
+        hists.append(hist)
+    return hists, part
+
+
+def _stats_dense(plan, hs):
+    """The launch's histograms (numpy, as _stats_launch orders them) -> [F, hstride, 4]."""
+    F, hstride = plan["F"], plan["hstride"]
+    if not len(plan["wide"]):
+        return hs[0].reshape(F, hstride, 4)
+    h = np.zeros((F, hstride, 4), np.int64)
+    if plan["Fn"]:
+        h[plan["narrow"], : plan["n_nb"] + 1] = hs[0].reshape(plan["Fn"], plan["n_nb"] + 1, 4)
+    h[plan["wide"], : plan["w_nb"] + 1] = hs[-1].reshape(len(plan["wide"]), plan["w_nb"] + 1, 4)
+    return h
+
+
 def column_stats(vals: torch.Tensor, y: torch.Tensor, w: torch.Tensor, bounds_list, binary: bool,
                  num_thr: float = 1.7976931348623157e308, nchunks: int | None = None):
     """vals [F, N] fp64 (column-major) on the GPU -> per column (cpos, cneg, wpos, wneg) numpy
-    arrays of length nb+1 (missing bin last) and moments (count, s1..s4, min, max)."""
+    arrays of length nb+1 (missing bin last) and moments (count, s1..s4, min, max).  Up to 16384
+    boundaries per column."""
     nat.require_gpu_native()
     F, N = vals.shape
-    dev = vals.device
-    bflat, boff = pack_bounds(bounds_list)
-    max_nb = int(np.max(np.diff(boff))) if F else 1
-    if max_nb > 1024:
-        raise ValueError("column_stats: more than 1024 bin boundaries per column")
-    hstride = max_nb + 1
+    plan = _stats_plan(bounds_list, vals.device)
+    boff = plan["boff"]
     wmax = float(w.abs().max().item()) if N else 1.0
     wscale = 2.0 ** min(40, math.floor(62 - math.log2(max(wmax, 1e-30) * max(N, 1))))
     nchunks = nchunks or max(1, min(256, (N + 65535) // 65536))
-    hist = torch.zeros(F * hstride * 4, dtype=torch.int64, device=dev)
-    part = torch.zeros(F * nchunks * 8, dtype=torch.float64, device=dev)
-    bt, ot = _dev_tensor(bflat, torch.float64, dev), _dev_tensor(boff, torch.int32, dev)
     unit_w = bool(N) and bool(torch.all(w[:N] == 1.0).item())
     posbits = pack_sel(y[:N], 1) if binary else None
-    rc = nat.call_hip("shifu_column_stats", vals, vals.stride(0), y, w, N, F, bt, ot, max_nb, int(binary), wscale,
-                      float(num_thr), hist, hstride, part, nchunks, int(unit_w), posbits, nat.stream_of(vals))
-    if rc:
-        raise RuntimeError(f"shifu_column_stats failed rc={rc}")
-    h = hist.view(F, hstride, 4).cpu().numpy()
+    hists, part = _stats_launch(plan, vals, y, w, N, binary, wscale, num_thr, nchunks, unit_w, posbits)
+    h = _stats_dense(plan, [t.cpu().numpy() for t in hists])
     p = part.view(F, nchunks, 8).cpu().numpy()
     out = []
     for f in range(F):
@@ -112,36 +184,28 @@ def column_stats_multi(vals_list, y: torch.Tensor, w: torch.Tensor, bounds_lists
     wscale = 2.0 ** min(40, math.floor(62 - math.log2(max(wmax, 1e-30) * max(N, 1))))
     nchunks = max(1, min(256, (N + 65535) // 65536))
     posbits = pack_sel(y[:N], 1) if binary else None
-    hists, parts, metas = [], [], []
+    hists, parts, plans = [], [], []
     for vals, bounds_list in zip(vals_list, bounds_lists):
-        F = vals.shape[0]
         hit = bounds_cache.get(id(bounds_list)) if bounds_cache is not None else None
         if hit is None or hit[0] is not bounds_list:
-            bflat, boff = pack_bounds(bounds_list)
-            max_nb = int(np.max(np.diff(boff))) if F else 1
-            if max_nb > 1024:
-                raise ValueError("column_stats: more than 1024 bin boundaries per column")
-            hit = (bounds_list, boff, max_nb, _dev_tensor(bflat, torch.float64, dev), _dev_tensor(boff, torch.int32, dev))
+            hit = (bounds_list, _stats_plan(bounds_list, dev))
             if bounds_cache is not None:
                 bounds_cache[id(bounds_list)] = hit
-        _, boff, max_nb, bt, ot = hit
-        hstride = max_nb + 1
-        hist = torch.zeros(F * hstride * 4, dtype=torch.int64, device=dev)
-        part = torch.zeros(F * nchunks * 8, dtype=torch.float64, device=dev)
-        rc = nat.call_hip("shifu_column_stats", vals, vals.stride(0), y, w, N, F, bt, ot, max_nb, int(binary), wscale,
-                          float(num_thr), hist, hstride, part, nchunks, int(unit_w), posbits, nat.stream_of(vals))
-        if rc:
-            raise RuntimeError(f"shifu_column_stats failed rc={rc}")
-        hists.append(hist)
+        hs, part = _stats_launch(hit[1], vals, y, w, N, binary, wscale, num_thr, nchunks, unit_w, posbits)
+        hists.append(hs)
         parts.append(part)
-        metas.append((F, hstride, boff))
-    H = torch.cat(hists).cpu().numpy()
+        plans.append(hit[1])
+    H = torch.cat([t for hs in hists for t in hs]).cpu().numpy()
     P = torch.cat(parts).cpu().numpy()
     res, ho, po = [], 0, 0
-    for F, hstride, boff in metas:
-        h = H[ho: ho + F * hstride * 4].reshape(F, hstride, 4)
+    for plan, hs in zip(plans, hists):
+        F = plan["F"]
+        pieces = []
+        for t in hs:
+            pieces.append(H[ho: ho + t.numel()])
+            ho += t.numel()
+        h = _stats_dense(plan, pieces)
         p = P[po: po + F * nchunks * 8].reshape(F, nchunks, 8)
-        ho += F * hstride * 4
         po += F * nchunks * 8
         mom = np.empty((F, 7), np.float64)
         for k in range(5):
@@ -149,7 +213,7 @@ def column_stats_multi(vals_list, y: torch.Tensor, w: torch.Tensor, bounds_lists
         mom[:, 5] = p[:, :, 5].min(1)
         mom[:, 6] = p[:, :, 6].max(1)
         mom[mom[:, 0] == 0] = (0, 0.0, 0.0, 0.0, 0.0, np.nan, np.nan)
-        res.append((h[:, :, :2].astype(np.int64), h[:, :, 2:4] / wscale, mom, boff))
+        res.append((h[:, :, :2].astype(np.int64), h[:, :, 2:4] / wscale, mom, plan["boff"]))
     return res
 
 
@@ -181,7 +245,8 @@ def normalize(vals: torch.Tensor, specs: list, out: torch.Tensor):
 
 
 def bin_codes(vals: torch.Tensor, is_cat, bounds_list, ncat, out: torch.Tensor):
-    """Tree bin codes uint8 [N, ldo] from column-major fp64 values."""
+    """Tree bin codes [N, ldo] from column-major fp64 values: ``out`` uint8 (every feature at most
+    256 bins) or int16 (up to 16384)."""
     nat.require_gpu_native()
     F, N = vals.shape
     dev = vals.device
@@ -189,10 +254,16 @@ def bin_codes(vals: torch.Tensor, is_cat, bounds_list, ncat, out: torch.Tensor):
     ip = np.zeros((F, 4), np.int32)
     for f in range(F):
         ip[f] = [int(is_cat[f]), boff[f], boff[f + 1] - boff[f], int(ncat[f])]
-    rc = nat.call_hip("shifu_bin_codes", vals, vals.stride(0), N, F, _dev_tensor(ip, torch.int32, dev),
+    if out.dtype not in (torch.uint8, torch.int16):
+        raise ValueError(f"bin_codes: uint8 or int16 output, not {out.dtype}")
+    nbmax = max([int(ncat[f]) + 1 if is_cat[f] else int(ip[f, 2]) for f in range(F)], default=1)
+    if nbmax > (256 if out.dtype == torch.uint8 else WIDE_NB):
+        raise ValueError(f"bin_codes: {nbmax} bins do not fit {out.dtype} codes")
+    name = "shifu_bin_codes" if out.dtype == torch.uint8 else "shifu_bin_codes_i16"
+    rc = nat.call_hip(name, vals, vals.stride(0), N, F, _dev_tensor(ip, torch.int32, dev),
                       _dev_tensor(bflat, torch.float64, dev), out, out.stride(0), nat.stream_of(vals))
     if rc:
-        raise RuntimeError(f"shifu_bin_codes failed rc={rc}")
+        raise RuntimeError(f"{name} failed rc={rc}")
     return out
 
 
