@@ -14,6 +14,13 @@ On a GPU run the bulk numeric columns of each block are parsed on the device ins
    a column-major fp64 block in HBM; fields outside the Clinger fast path come back as a short list
    the host finishes with its own strtod path (``shifu_parse_fields``), blank lines are dropped.
 
+4. ``shifu_csv_cat_encode`` (``ops/csrc/csv_cat_kernels.hip``) turns the field bounds of the
+   categorical (string) columns into int32 dictionary codes in HBM and a per-column distinct list;
+   the host slices the few dictionary strings out of the page-locked block.  A column whose table
+   overflowed or met a hash collision, and the numeric columns the host must see (weight, filter
+   inputs), are parsed on the host from their gathered fields (``shifu_gather_fields``), for that
+   block only.  ``shifu.data.gpuParse.categorical = false`` sends every host column that way.
+
 The result is bit-identical to the host parse (tests/test_gpu_parse.py).  Parsed columns stay in
 HBM as :class:`DeviceBlock` rows: ``stats`` batches and the ``norm`` K5 pass read them in place
 (``device_rows``); anything that asks for host values gets one D2H copy of the block.
@@ -32,6 +39,10 @@ _log = get_logger("data.gpu_parse")
 # largest block the device parse takes: field bounds are int32 offsets into the block (+64 B pad)
 BLOCK_LIMIT = (1 << 31) - 64
 FB_CAP = 1 << 20          # fallback fields per block before the whole block is parsed on the host
+# dictionary table slots per categorical column and block: categorical model inputs hold tens to a
+# few thousand values; 2^16 slots keep probe runs short up to ~30k distinct values, and an id-like
+# column (more than that per block) overflows within 64 probes and is parsed on the host instead
+CAT_CAP = 1 << 16
 MAX_TOKENS, TOKEN_BYTES = 8, 15
 
 
@@ -71,6 +82,13 @@ class DevRef:
 
     def __len__(self):
         return int(self.block.D.shape[1])
+
+    def __iter__(self):
+        return iter(self.host())
+
+    def __array__(self, dtype=None, copy=None):
+        a = self.host()
+        return a if dtype is None else a.astype(dtype, copy=False)
 
 
 def device_rows(cols, dev):
@@ -140,16 +158,23 @@ class GpuBlockParser:
         # the host-parsed columns: the kernel hands back their field bounds, the host parses just
         # those bytes (one short line per row) instead of scanning the whole block
         self.host_cols = [c for c, k in enumerate(self.kinds_host) if k]
-        self.kinds_mini = [self.kinds_host[c] for c in self.host_cols] + [0]
         mslot = np.full(len(kinds), -1, np.int32)
         mslot[self.host_cols] = np.arange(len(self.host_cols), dtype=np.int32)
         self.mslot = torch.as_tensor(mslot, device=self.dev) if self.host_cols else None
+        # the categorical (string) ones among them are dictionary-coded on the device
+        # (ops/csrc/csv_cat_kernels.hip) unless shifu.data.gpuParse.categorical = false
+        from ..config import environment
+        cat_on = str(environment.get("shifu.data.gpuParse.categorical", "auto")).lower() not in ("false", "0", "off")
+        self.cat_slots = [j for j, c in enumerate(self.host_cols) if self.kinds_host[c] == 2] if cat_on else []
+        self.cat_cap, self.hash_bits = CAT_CAP, 64
+        self.empty_missing = not list(missing) or any(not str(t).strip(" \t\r") for t in missing)
         self.fb = torch.empty(4 * FB_CAP, dtype=torch.long, device=self.dev)
         self.fb_n = torch.zeros(1, dtype=torch.int32, device=self.dev)
         self.stream = None
         self.h2d_stream = None
-        self.stats = {"blocks": 0, "fallback_fields": 0, "host_blocks": 0, "bytes": 0}
-        self.times = {"h2d": 0.0, "index": 0.0, "kernel": 0.0, "fallback": 0.0, "host_cols": 0.0}
+        self.stats = {"blocks": 0, "fallback_fields": 0, "host_blocks": 0, "bytes": 0, "cat_device_cols": 0,
+                      "cat_overflow_cols": 0}
+        self.times = {"h2d": 0.0, "index": 0.0, "kernel": 0.0, "fallback": 0.0, "host_cols": 0.0, "cat_encode": 0.0}
 
     def uploads(self, blocks):
         """(key, block) -> (key, block, device copy of the block): the H2D stage of the streamed
@@ -181,7 +206,8 @@ class GpuBlockParser:
     def parse(self, data, nthreads: int, dbuf=None):
         """``data``: a memoryview of complete lines inside a page-locked uint8 ndarray (or any
         buffer: then it is staged) -> the host parser's (n, bad, {column: (kind, values, dict)})
-        with the GPU columns as ``("num", DevRef, [])``."""
+        with the GPU columns as ``("num", DevRef, [])`` and the categorical columns coded on the
+        device as ``("str", DevRef of int32 codes, dictionary)``."""
         import torch
         from ..ops import _native as nat
         from .reader import parse_block
@@ -196,11 +222,12 @@ class GpuBlockParser:
             n, bad, out = self._parse(data, nthreads, dbuf)
             self.stream.synchronize()
         consumer = torch.cuda.default_stream(self.dev)
-        for c in self.gpu_cols:
-            ref = out[c][1]
-            if isinstance(ref, DevRef):
+        seen = set()
+        for v in out.values():
+            ref = v[1]
+            if isinstance(ref, DevRef) and id(ref.block) not in seen:
+                seen.add(id(ref.block))
                 ref.block.D.record_stream(consumer)     # freed by the consumer: reuse waits for it
-                break
         return n, bad, out
 
     def _parse(self, data, nthreads: int, dbuf=None):
@@ -267,22 +294,12 @@ class GpuBlockParser:
         else:
             n, bad, out = int((~blank).sum()), 0, {}
             if nh:
-                mo = moffs.cpu().numpy()
-                # the kernel writes only column 0's bounds on a blank line: the other entries are
-                # whatever the allocator left there, so they must not size the gather buffer
-                if blank.any():
-                    mo[:, blank, :] = 0
-                cap =int(np.clip(mo[..., 1] - mo[..., 0], 0, None).sum()) + nl * (nh + 3)
-                mini = np.empty(cap, np.uint8)
-                nb = nat.rt().shifu_gather_fields(addr, mo.ctypes.data, nl, nh, fl.ctypes.data,
-                                                  self.delim.encode(), mini.ctypes.data, cap)
-                if nb < 0:
-                    raise RuntimeError("GPU parse: gathering the host columns failed")
-                n2, _, o2 = parse_block(memoryview(mini[:nb]), self.delim, self.kinds_mini, self.missing,
-                                        max(1, min(nthreads, nb >> 20)))
-                if n2 != n:
-                    raise RuntimeError(f"GPU parse: {n} rows framed, {n2} host-column rows")
-                out = {c: o2[j] for j, c in enumerate(self.host_cols)}
+                rest = list(range(nh))
+                if self.cat_slots:
+                    out, over = self._cat_encode(data, dbuf, L, moffs, lflags, nl, blank)
+                    rest = [j for j in rest if j not in self.cat_slots or j in over]
+                if rest:
+                    out.update(self._gather_parse(data, addr, moffs, rest, fl, blank, nl, n, nthreads))
             self.stats["gathered_blocks"] = self.stats.get("gathered_blocks", 0) + 1
         if vals.shape[1] != n:
             raise RuntimeError(f"GPU parse framed {vals.shape[1]} rows, host parser {n}")
@@ -290,6 +307,74 @@ class GpuBlockParser:
         blk = DeviceBlock(vals)
         out.update({c: ("num", DevRef(blk, j), []) for j, c in enumerate(self.gpu_cols)})
         return n, bad, out
+
+    def _gather_parse(self, data, addr, moffs, slots, fl, blank, nl, n, nthreads):
+        """The host columns ``slots`` (indices into ``host_cols``) from their field bounds: the
+        bounds come to the host, the fields are gathered into one short line per row and the host
+        parser reads just those bytes."""
+        import torch
+        from ..ops import _native as nat
+        from .reader import parse_block
+        k = len(slots)
+        sel = moffs if k == len(self.host_cols) else \
+            moffs.index_select(0, torch.as_tensor(slots, dtype=torch.long, device=self.dev))
+        mo = sel.cpu().numpy()
+        # the kernel writes only column 0's bounds on a blank line: the other entries are
+        # whatever the allocator left there, so they must not size the gather buffer
+        if blank.any():
+            mo[:, blank, :] = 0
+        cap = int(np.clip(mo[..., 1] - mo[..., 0], 0, None).sum()) + nl * (k + 3)
+        mini = np.empty(cap, np.uint8)
+        nb = nat.rt().shifu_gather_fields(addr, mo.ctypes.data, nl, k, fl.ctypes.data,
+                                          self.delim.encode(), mini.ctypes.data, cap)
+        if nb < 0:
+            raise RuntimeError("GPU parse: gathering the host columns failed")
+        kinds_mini = [self.kinds_host[self.host_cols[j]] for j in slots] + [0]
+        n2, _, o2 = parse_block(memoryview(mini[:nb]), self.delim, kinds_mini, self.missing,
+                                max(1, min(nthreads, nb >> 20)))
+        if n2 != n:
+            raise RuntimeError(f"GPU parse: {n} rows framed, {n2} host-column rows")
+        return {self.host_cols[j]: o2[i] for i, j in enumerate(slots)}
+
+    def _cat_encode(self, data, dbuf, L, moffs, lflags, nl, blank):
+        """Dictionary codes of the categorical columns on the device (csv_cat_kernels.hip) ->
+        ({column: ("str", DevRef of its int32 codes, dictionary)}, host-column slots whose table
+        overflowed or met a hash collision: the caller parses those on the host).  Only the counts,
+        the flags and the used part of the distinct list come back; the strings are sliced out of
+        the host copy of the block."""
+        import torch
+        from ..ops import _native as nat
+        t0 = time.perf_counter()
+        slots, nc, cap = self.cat_slots, len(self.cat_slots), int(self.cat_cap)
+        need = int(nat.hip().shifu_csv_cat_ws_bytes(nc, cap, nl))
+        if getattr(self, "_cat_ws", None) is None or self._cat_ws.numel() < need or self._cat_dl.numel() < 2 * nc * cap:
+            self._cat_ws = torch.empty(need + (need >> 2), dtype=torch.uint8, device=self.dev)
+            self._cat_dl = torch.empty(2 * nc * cap, dtype=torch.int32, device=self.dev)
+            self._cat_cf = torch.empty(2 * nc, dtype=torch.int32, device=self.dev)
+            self._cat_cols = torch.as_tensor(slots, dtype=torch.int32, device=self.dev)
+        cf = self._cat_cf
+        codes = torch.empty((nc, nl), dtype=torch.int32, device=self.dev)
+        nat.call_hip("shifu_csv_cat_encode", dbuf, L, moffs, lflags, nl, self._cat_cols, nc, self.ntok, self.toks,
+                     int(self.empty_missing), cap, int(self.hash_bits), self._cat_ws, codes, nl, self._cat_dl,
+                     cf[:nc], cf[nc:], nat.stream_of(dbuf))
+        h = cf.cpu().numpy()
+        counts, flags = h[:nc].astype(np.int64), h[nc:]
+        base = np.concatenate([[0], np.cumsum(counts)])
+        dl = self._cat_dl[: 2 * int(base[-1])].cpu().numpy().reshape(-1, 2)
+        if blank.any():
+            codes = codes[:, torch.as_tensor(np.flatnonzero(~blank), device=self.dev)]
+        blk = DeviceBlock(codes)
+        out, over = {}, set()
+        for i, j in enumerate(slots):
+            if flags[i]:
+                over.add(j)
+                continue
+            d = [bytes(data[a:a + m]).decode("utf-8", errors="replace") for a, m in dl[base[i]:base[i + 1]].tolist()]
+            out[self.host_cols[j]] = ("str", DevRef(blk, i), d)
+        self.stats["cat_device_cols"] += nc - len(over)
+        self.stats["cat_overflow_cols"] += len(over)
+        self.times["cat_encode"] += time.perf_counter() - t0
+        return out, over
 
     def _newlines(self, dbuf, L: int):
         """int64 positions of every '\\n' in dbuf[:L] (own kernels, csv_kernels.hip: segment
@@ -314,7 +399,8 @@ class GpuBlockParser:
         s = self.stats
         tt = " ".join(f"{k} {v:.2f}s" for k, v in self.times.items())
         return (f"GPU parse: {s['blocks']} blocks, {s['bytes'] / 1e9:.1f} GB, {s['fallback_fields']} fallback fields, "
-                f"{s['host_blocks']} host blocks; {tt}")
+                f"{s['host_blocks']} host blocks, {s['cat_device_cols']} categorical columns coded on the device "
+                f"({s['cat_overflow_cols']} on the host after an overflow); {tt}")
 
     def _host_framing(self, data, nthreads, vals):
         """The host parser over the whole block for the host columns (row framing, bad rows)."""

@@ -364,6 +364,8 @@ def table_from_parts(header: list, kinds: list, parts: list, data_path: str = ""
             gdict, remapped = {}, []
             for p in parts:
                 _, codes, d = p[2][ci]
+                if not isinstance(codes, np.ndarray):      # coded on the GPU (DevRef): one D2H per block
+                    codes = codes.host()
                 lut = np.array([gdict.setdefault(s, len(gdict)) for s in d] + [-1], dtype=np.int32)
                 remapped.append(lut[np.where(codes >= 0, codes, len(d))])
             cols[name] = Column(name, "str", np.concatenate(remapped) if remapped else np.empty(0, np.int32),

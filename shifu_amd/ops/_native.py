@@ -55,6 +55,9 @@ HIP_SIGNATURES = {
     "shifu_split_bf16_rows": "plli" "pl" "ii" "s",
     # csv_kernels.hip
     "shifu_csv_gpu_parse": "pppl" "pi" "pl" "p" "pip" "iiP" "pp" "s",
+    # csv_cat_kernels.hip (dictionary codes of the categorical columns of a parsed block)
+    "shifu_csv_cat_ws_bytes": ("iil", "l"),
+    "shifu_csv_cat_encode": "pl" "ppl" "pi" "iPi" "ii" "p" "pl" "ppp" "s",
     # autotype_kernels.hip (init -autotype on the device)
     "shifu_at_gpu_caps": "p",
     "shifu_at_gpu_codes": "pppl" "i" "pl" "p" "iiP" "iiP" "s",
