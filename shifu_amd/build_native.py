@@ -27,7 +27,8 @@ ARCH = os.environ.get("SHIFU_OFFLOAD_ARCH", "gfx950")
 # per-source extra hipcc flags.  New kernels are compiled without the packed-fp32 VALU forms
 # (v_pk_*_f32); the older sources keep the flags their measurements were taken with
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_FLAGS = {"gbdt_wide_kernels.hip": NO_PK_F32, "gbdt_mc_kernels.hip": NO_PK_F32}
+EXTRA_FLAGS = {"gbdt_wide_kernels.hip": NO_PK_F32, "gbdt_mc_kernels.hip": NO_PK_F32,
+               "mlp_small.hip": NO_PK_F32}
 
 
 def _hipcc() -> str:

@@ -535,7 +535,10 @@ class MLPTrainer:
         self.wgrad_ring = os.environ.get("SHIFU_WGRAD_RING", "1") != "0"
         self.fused_head = self._head_eligible()
         self.strip_head = self.fused_head and self._strip_head_eligible()
+        self.fused_small = self._small_eligible()
         self.err_acc = torch.zeros(2, dtype=torch.float64, device=self.device)
+        # error sums of the second chunk lane (fused small-net step: no atomics, added in a fixed order)
+        self._small_err2 = torch.zeros(2, dtype=torch.float64, device=self.device) if self.fused_small else None
         # dropout (NNMaster.dropoutNodes :531-556, FloatFlatNetwork.computeLayer :205-215): each
         # iteration drops hidden nodes with DropoutRate and inputs with 0.4*DropoutRate and scales
         # kept outputs by 1/(1-rate).  Realised as a per-column scale of the NEXT layer's weights
@@ -608,6 +611,13 @@ class MLPTrainer:
             ws["gw_slab"] = torch.empty(tiles * kp[L], dtype=torch.float32, device=self.device)
             ws["err_slab"] = torch.empty(tiles * 2, dtype=torch.float64, device=self.device)
             ws["gw_part"] = torch.empty(-(-tiles // 128) * kp[L], dtype=torch.float32, device=self.device)
+        # fused small-net step (ops/csrc/mlp_small.hip): one gradient row + one error pair per block
+        ws["small_slab"] = ws["small_err"] = None
+        if self.gpu and self.fused_small:
+            from ..ops import _native as nat
+            g = nat.hip().shifu_mlp_small_rows(rows)
+            ws["small_slab"] = torch.empty(g * self.params.numel, dtype=torch.float32, device=self.device)
+            ws["small_err"] = torch.empty(g * 2, dtype=torch.float64, device=self.device)
         # bf16 output deltas of the any-shape output path (operand of the output-layer wgrad)
         ws["ldl"] = round_up(self.spec.n_out, 8)
         ws["outd"] = (torch.empty(rows, ws["ldl"], dtype=torch.bfloat16, device=self.device)
@@ -680,6 +690,8 @@ class MLPTrainer:
         side.wait_stream(main)                     # bf16 weights, zeroed grads, the rows
         with torch.cuda.stream(side):
             g2.zero_()
+            if self.fused_small:
+                self._small_err2.zero_()
         g1 = self.grad
         # stagger (opt-in; measured 299 vs 308M rows/s free-running): chunk i's forward starts once
         # chunk i-1's forward is done, so each lane's forward (fwd GEMMs + head) overlaps the other
@@ -701,6 +713,8 @@ class MLPTrainer:
             fwd_done = ev
         main.wait_stream(side)
         self.grad.add_(g2)
+        if self.fused_small:
+            self.err_acc.add_(self._small_err2)
 
     def _grad_ready(self, layer: int) -> None:
         """Layer ``layer``'s gradient is final (last chunk's wgrad enqueued): launch the buckets that
@@ -738,6 +752,29 @@ class MLPTrainer:
         return bool(kp[L] == 256 and kp[L - 1] == 512 and a1 == a2 and
                     ACT_IDS[a1] in ACT_DERIV_FROM_OUTPUT and a1 != "ptanh")
 
+    def _small_eligible(self) -> bool:
+        """Fused one-kernel gradient step of a small net (ops/csrc/mlp_small.hip): forward, output
+        neuron, loss, deltas, dgrad and every wgrad in one launch per chunk, X read once, nothing
+        but the gradient written.  1 or 2 hidden layers of <= 64 nodes, one output, padded input
+        width 128 or 256 (the kernel's LDS budget), hidden activations whose derivative follows
+        from the output (not ptanh).  Dropout and feature subsets reach it through the prepared
+        weights like every other engine.  Opt-in: SHIFU_MLP_FUSED_SMALL=1."""
+        sp = self.spec
+        L = len(sp.hidden)
+        if self.device.type != "cuda" or os.environ.get("SHIFU_MLP_FUSED_SMALL", "0") != "1":
+            return False
+        acts_ok = all(ACT_IDS[a] in ACT_DERIV_FROM_OUTPUT and a != "ptanh" for a in sp.acts)
+        return bool(L in (1, 2) and max(sp.hidden) <= 64 and min(sp.hidden) >= 1 and sp.n_out == 1 and
+                    sp.layer_kpad[0] <= 256 and acts_ok and not self.wide_out)
+
+    def _small_args(self, wb):
+        """(W2, h2, act ids, flat spots) of the fused small-net kernels."""
+        sp = self.spec
+        two = len(sp.hidden) == 2
+        a1, a2 = sp.acts[0], sp.acts[1] if two else sp.acts[0]
+        return (wb[1] if two else None, sp.hidden[1] if two else 0, ACT_IDS[a1], ACT_IDS[a2],
+                sp.flat_spot(a1), sp.flat_spot(a2) if two else 0.0)
+
     def _chunk_hip(self, data: TrainData, r0: int, r1: int, wb, wt, x_dev=None, lane: int = 0, fwd_event=None):
         from ..ops import _native as nat
         sp, kp = self.spec, self.spec.layer_kpad
@@ -748,6 +785,20 @@ class MLPTrainer:
         wv = self.params.views(self._wflat)
         x = data.x[r0:r1] if x_dev is None else x_dev
         st = nat.stream_of(x)
+        if self.fused_small:
+            # the whole chunk in one launch + the fixed-order slab reduction into this lane's
+            # gradient and error sums
+            w2, h2, a1, a2, f1, f2 = self._small_args(wb)
+            nat.call_hip("shifu_mlp_small_step", x, x.stride(0), wb[0], w2, wv[L].data_ptr(), data.y[r0:r1].data_ptr(),
+                         data.s[r0:r1].data_ptr() if data.s is not None else None, ws["small_slab"],
+                         ws["small_err"], self.grad, self.err_acc if lane == 0 else self._small_err2,
+                         self.params.numel, mc, kp[0], sp.hidden[0], h2, a1, a2, ACT_IDS[sp.out_act], sp.loss_id,
+                         f1, f2, sp.flat_spot(sp.out_act), st)
+            if fwd_event is not None:
+                fwd_event.record()
+            for l in range(L, -1, -1):
+                self._grad_ready(l)
+            return
         acts = [x] + [a[:mc] for a in ws["acts"]]
         dels = [None] + [d[:mc] for d in ws["deltas"]]
         ders = [None] + [(d[:mc] if d is not None else None) for d in ws["derivs"]]
@@ -990,6 +1041,14 @@ class MLPTrainer:
         wb, _ = self._weights_bf16(train=False)
         wv = self.params.views()
         st = nat.stream_of(xpad)
+        if self.fused_small:            # forward-only instantiation of the fused small-net kernel
+            w2, h2, a1, a2, _, _ = self._small_args(wb)
+            for r0 in range(0, n, self.chunk_rows):
+                r1 = min(n, r0 + self.chunk_rows)
+                nat.call_hip("shifu_mlp_small_forward", xpad[r0:r1].data_ptr(), xpad.stride(0), wb[0], w2,
+                             wv[L].data_ptr(), out[r0:r1].data_ptr(), r1 - r0, kp[0], sp.hidden[0], h2, a1, a2,
+                             ACT_IDS[sp.out_act], st)
+            return out
         ws = self._workspace(min(self.chunk_rows, n))
         gscratch = torch.zeros(sp.n_out, kp[L], dtype=torch.float32, device=self.device)
         escratch = torch.zeros(2, dtype=torch.float64, device=self.device)

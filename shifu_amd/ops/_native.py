@@ -80,6 +80,10 @@ HIP_SIGNATURES = {
     "shifu_strip_head": "plpli" "pl" "plpl" "iiii" "pi" "ppppp" "iiii" "fff" "s",
     "shifu_strip_head_rows": ("i", "i"),
     "shifu_strip_head_set_dbg_rows": "p",
+    # fused gradient step / forward of small MLPs (mlp_small.hip)
+    "shifu_mlp_small_step": "plpp" "ppp" "pppp" "l" "iiii" "iiii" "fff" "s",
+    "shifu_mlp_small_forward": "plpp" "pp" "iiii" "iii" "s",
+    "shifu_mlp_small_rows": ("i", "i"),
     # gbdt_kernels.hip
     "shifu_gbdt_hist": "pli" "ppp" "i" "pipi" "dd" "l" "i" "s",
     "shifu_gbdt_hist_root_quad": "plpppipids",

@@ -145,6 +145,41 @@ __device__ __forceinline__ float act_deriv_pre(int act, float b) {
   }
 }
 
+// 8 bf16 <-> 8 floats (one 16-byte row piece of the MLP row kernels)
+__device__ __forceinline__ void unpack8(const uint4 v, float* f) {
+  f[0] = bf2f(v.x & 0xffff); f[1] = bf2f(v.x >> 16); f[2] = bf2f(v.y & 0xffff); f[3] = bf2f(v.y >> 16);
+  f[4] = bf2f(v.z & 0xffff); f[5] = bf2f(v.z >> 16); f[6] = bf2f(v.w & 0xffff); f[7] = bf2f(v.w >> 16);
+}
+__device__ __forceinline__ uint4 pack8(const float* f) {
+  uint4 v;
+  v.x = pack_bf16x2(f[0], f[1]);
+  v.y = pack_bf16x2(f[2], f[3]);
+  v.z = pack_bf16x2(f[4], f[5]);
+  v.w = pack_bf16x2(f[6], f[7]);
+  return v;
+}
+
+// One output neuron of one row: delta and error contribution (SubGradient.java:224-311) from the
+// pre-activation z, the output a, the target y and the row weight s.  loss 0 squared, 1 log,
+// 2 absolute; loss >= 3: the same deltas with the TF objective as the error.  single: n_out == 1.
+__device__ __forceinline__ void out_loss_delta(int out_act, int loss, bool single, float flat_out, float z, float a,
+                                               float y, float s, float& dlt, float& contrib) {
+  const float e = y - a;
+  const int lm = loss % 3;
+  if (lm == 1) {              // log
+    dlt = e * s;
+    const float ac = fminf(fmaxf(a, 1e-7f), 1.f - 1e-7f);
+    contrib = loss >= 3 ? -(__logf(a + 1e-7f) * y + __logf(1.f - a + 1e-7f) * (1.f - y)) * s
+              : single ? -(__logf(ac) * y + __logf(1.f - ac) * (1.f - y)) : -(__logf(ac) * y * s);
+  } else if (lm == 2) {       // absolute
+    dlt = (y < a ? 1.f : -1.f) * (act_deriv_out(out_act, a) + flat_out) * s;
+    contrib = fabsf(e) * s;
+  } else {                    // squared (default)
+    dlt = (act_deriv_pre(out_act, z) + flat_out) * e * s;
+    contrib = loss >= 3 ? e * e * s : (e * s) * (e * s);
+  }
+}
+
 // Streaming row loop with U independent loads in flight per thread: the stats/quantile kernels
 // are HBM-bound single passes, and one outstanding 8-byte load per lane leaves far too few bytes
 // in flight per CU (Little's law at ~1 us HBM latency); loading U rows before processing any

@@ -19,19 +19,6 @@ struct OutArgs {
   float flat_out, flat_hid;
 };
 
-__device__ __forceinline__ void unpack8(const uint4 v, float* f) {
-  f[0] = bf2f(v.x & 0xffff); f[1] = bf2f(v.x >> 16); f[2] = bf2f(v.y & 0xffff); f[3] = bf2f(v.y >> 16);
-  f[4] = bf2f(v.z & 0xffff); f[5] = bf2f(v.z >> 16); f[6] = bf2f(v.w & 0xffff); f[7] = bf2f(v.w >> 16);
-}
-__device__ __forceinline__ uint4 pack8(const float* f) {
-  uint4 v;
-  v.x = pack_bf16x2(f[0], f[1]);
-  v.y = pack_bf16x2(f[2], f[3]);
-  v.z = pack_bf16x2(f[4], f[5]);
-  v.w = pack_bf16x2(f[6], f[7]);
-  return v;
-}
-
 // LPR lanes per row (KH = 8*LPR), RPS = 64/LPR rows per wave step, U steps in flight.
 template <int NOUT, int LPR>
 __global__ __launch_bounds__(256) void mlp_output_kernel(OutArgs p) {
@@ -79,22 +66,9 @@ __global__ __launch_bounds__(256) void mlp_output_kernel(OutArgs p) {
         for (int off = LPR / 2; off > 0; off >>= 1) z += __shfl_xor(z, off, 64);
         const float a = act_fwd(p.out_act, z);
         const float y = yv[u][o];
-        const float e = y - a;
         if (p.P && valid && li == 0) p.P[(size_t)m * p.ldp + o] = a;
         float contrib;
-        const int lm = p.loss % 3;                // loss >= 3: same deltas, TF objective as the error
-        if (lm == 1) {              // log
-          dlt[o] = e * s;
-          const float ac = fminf(fmaxf(a, 1e-7f), 1.f - 1e-7f);
-          contrib = p.loss >= 3 ? -(__logf(a + 1e-7f) * y + __logf(1.f - a + 1e-7f) * (1.f - y)) * s
-                    : NOUT == 1 ? -(__logf(ac) * y + __logf(1.f - ac) * (1.f - y)) : -(__logf(ac) * y * s);
-        } else if (lm == 2) {       // absolute
-          dlt[o] = (y < a ? 1.f : -1.f) * (act_deriv_out(p.out_act, a) + p.flat_out) * s;
-          contrib = fabsf(e) * s;
-        } else {                    // squared (default)
-          dlt[o] = (act_deriv_pre(p.out_act, z) + p.flat_out) * e * s;
-          contrib = p.loss >= 3 ? e * e * s : (e * s) * (e * s);
-        }
+        out_loss_delta(p.out_act, p.loss, NOUT == 1, p.flat_out, z, a, y, s, dlt[o], contrib);
         if (!valid) dlt[o] = 0.f;
         if (valid && li == 0) esum += contrib;
       }
@@ -188,7 +162,6 @@ __global__ __launch_bounds__(256) void mlp_output_wide_kernel(WideArgs p) {
   const long wave0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
   const int ngroups = p.KH / 8;
-  const int lm = p.loss % 3;
   double esum = 0.0, wsum = 0.0;
   for (long m = wave0; m < p.M; m += nwaves) {
     const bf16_t* hrow = p.H + (size_t)m * p.ldh;
@@ -222,20 +195,8 @@ __global__ __launch_bounds__(256) void mlp_output_wide_kernel(WideArgs p) {
         }
         const float a = act_fwd(p.out_act, z[o]);
         const float y = p.Y[(size_t)m * p.ldy + oi];
-        const float e = y - a;
         float d, contrib;
-        if (lm == 1) {
-          d = e * s;
-          const float ac = fminf(fmaxf(a, 1e-7f), 1.f - 1e-7f);
-          contrib = p.loss >= 3 ? -(__logf(a + 1e-7f) * y + __logf(1.f - a + 1e-7f) * (1.f - y)) * s
-                    : p.n_out == 1 ? -(__logf(ac) * y + __logf(1.f - ac) * (1.f - y)) : -(__logf(ac) * y * s);
-        } else if (lm == 2) {
-          d = (y < a ? 1.f : -1.f) * (act_deriv_out(p.out_act, a) + p.flat_out) * s;
-          contrib = fabsf(e) * s;
-        } else {
-          d = (act_deriv_pre(p.out_act, z[o]) + p.flat_out) * e * s;
-          contrib = p.loss >= 3 ? e * e * s : (e * s) * (e * s);
-        }
+        out_loss_delta(p.out_act, p.loss, p.n_out == 1, p.flat_out, z[o], a, y, s, d, contrib);
         if (lane == 0) {
           esum += contrib;
           dl[oi] = d;
