@@ -756,8 +756,8 @@ class MLPTrainer:
         """Fused one-kernel gradient step of a small net (ops/csrc/mlp_small.hip): forward, output
         neuron, loss, deltas, dgrad and every wgrad in one launch per chunk, X read once, nothing
         but the gradient written.  1 or 2 hidden layers of <= 64 nodes, one output, padded input
-        width 128 or 256 (the kernel's LDS budget), hidden activations whose derivative follows
-        from the output (not ptanh).  Dropout and feature subsets reach it through the prepared
+        width 128 or 256 (128-row tile) or 384 or 512 (64-row tile; the kernel's LDS budget), hidden
+        activations whose derivative follows from the output (not ptanh).  Dropout and feature subsets reach it through the prepared
         weights like every other engine.  Opt-in: SHIFU_MLP_FUSED_SMALL=1."""
         sp = self.spec
         L = len(sp.hidden)
@@ -765,7 +765,7 @@ class MLPTrainer:
             return False
         acts_ok = all(ACT_IDS[a] in ACT_DERIV_FROM_OUTPUT and a != "ptanh" for a in sp.acts)
         return bool(L in (1, 2) and max(sp.hidden) <= 64 and min(sp.hidden) >= 1 and sp.n_out == 1 and
-                    sp.layer_kpad[0] <= 256 and acts_ok and not self.wide_out)
+                    sp.layer_kpad[0] <= 512 and acts_ok and not self.wide_out)
 
     def _small_args(self, wb):
         """(W2, h2, act ids, flat spots) of the fused small-net kernels."""

@@ -1,6 +1,7 @@
 // Fused one-kernel gradient step for small MLPs (gfx950 / CDNA4): 1 or 2 hidden layers of at most
-// 64 nodes, one output, first-layer padded input width kp0 = 128 or 256 (the upper bound: at
-// kp0 = 256 the 128-row tile, the weights and the delta tiles fill 153 of the CU's 160 KiB of LDS).
+// 64 nodes, one output, first-layer padded input width kp0 = 128 or 256 (mlp_small_kernel: at
+// kp0 = 256 the 128-row tile, the weights and the delta tiles fill 153 of the CU's 160 KiB of LDS)
+// or 384 or 512 (mlp_small_wide_kernel, the same step on a 64-row tile, described where it stands).
 //
 // One launch per row chunk does forward, output neuron, loss, deltas, hidden dgrad and every
 // layer's wgrad.  X is read from HBM once; no activation or delta goes to HBM.
@@ -23,6 +24,8 @@
 //           pair; small_reduce_kernel adds the rows in block order into the gradient.  No atomics:
 //           gradient and error are bitwise reproducible.
 // Rows are addressed with 64-bit bases, so a chunk may be any size an int row count allows.
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -390,6 +393,363 @@ __global__ __launch_bounds__(SM_T) void mlp_small_kernel(SmallArgs p) {
   }
 }
 
+// ---- the wide variant: kp0 = 384 or 512 on a 64-row tile -------------------------------------
+// W1 and the X tile grow with kp0, so the tile shrinks to 64 rows: at kp0 = 512 W1 and X take
+// 64 KiB each.  The algorithm, the fragment layouts and the swizzles are those of mlp_small_kernel
+// (sm_xoff's and W1's XORs touch only the low 4 bits of a chunk index, and both pitches hold a
+// whole number of 16-chunk groups); what differs:
+//   split   4 waves, wave w owns the ONE 16-row strip [16 w, 16 w + 16) of the tile: xf[KS] is 64
+//           registers at KS = 16, dW1's slice [64][kp0 / 4] 128 accumulator registers, every other
+//           per-row value half of the 128-row kernel's.  8 waves with kp0 / 8 column slices would
+//           halve the accumulators, but the transposed forward needs all of a row's nodes in one
+//           wave: with 64 rows only 4 waves have a strip, and the other 4 would idle through the
+//           forward (or the strips shrink to 8 rows, half-empty MFMAs).  The price of one strip per
+//           wave is that a W1 fragment read feeds one MFMA, not two.
+//   LDS     kp0 = 512, two layers: W1 [0, 64K), W2 [64K, 72K), X tile [72K, 136K), D1 [136K, 144K),
+//           H1 [144K, 152K), D2 [152K, 160K): exactly the CU's 160 KiB.  The fp32 output weights,
+//           the output bias and the layer-2 biases a lane needs (16 + 1 + 16 values, they depend
+//           on lane >> 4 only) live in registers, which is what makes that build fit; every wide
+//           build does the same.  One-layer builds hold no W2, H1 and D2.
+//   loads   xf is free once the layer-1 loop has used it, so the next tile's rows are requested
+//           there and land during layer 2, the backward row math and the wgrad (the 128-row kernel
+//           has no registers for that and requests them after the first barrier).
+//   wgrad   two 32-row MFMA steps per tile instead of four; the D fragments are held and the X
+//           fragments stream, which keeps the two-layer kp0 = 512 build out of scratch.
+//   VALU    the activation id is switched on once per 16 values (sw_with_act), not once per value:
+//           the counters showed 2400 VALU instructions and 380 branches per strip against 96 MFMAs.
+constexpr int SW_TILE = 64;        // rows per block tile (16 per wave)
+constexpr int SW_TILE_B = SW_TILE * 64 * 2;   // one [64][64] bf16 tile
+
+__host__ __device__ constexpr int sw_lds_bytes(int kp0, bool two, bool train) {
+  return 64 * kp0 * 2 + (two ? 8192 : 0) + (train ? SW_TILE * kp0 * 2 + (two ? 3 : 1) * SW_TILE_B : 0);
+}
+
+// f(integral constant of the activation id): ONE switch for a strip's 16 values.  The id is uniform,
+// but act_fwd / act_deriv_out switch per value: about 370 scalar branches per 16-row strip, a
+// quarter of a wave's cycles with one wave per SIMD.
+template <typename F>
+__device__ __forceinline__ void sw_with_act(int act, F&& f) {
+  switch (act) {
+    case ACT_SIGMOID: f(std::integral_constant<int, ACT_SIGMOID>{}); break;
+    case ACT_TANH: f(std::integral_constant<int, ACT_TANH>{}); break;
+    case ACT_LINEAR: f(std::integral_constant<int, ACT_LINEAR>{}); break;
+    case ACT_RELU: f(std::integral_constant<int, ACT_RELU>{}); break;
+    case ACT_LEAKYRELU: f(std::integral_constant<int, ACT_LEAKYRELU>{}); break;
+    case ACT_LOG: f(std::integral_constant<int, ACT_LOG>{}); break;
+    case ACT_LEAKYRELU_TF: f(std::integral_constant<int, ACT_LEAKYRELU_TF>{}); break;
+  }
+}
+
+template <int KS, bool TWO, bool TRAIN>
+__global__ __launch_bounds__(SM_T) void mlp_small_wide_kernel(SmallArgs p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int KP0 = 32 * KS, PITCH = KP0 * 2, CB = KS / 2;
+  constexpr int oW1 = 0, oW2 = 64 * PITCH, oX = oW2 + (TWO ? 8192 : 0), oD1 = oX + SW_TILE * PITCH,
+                oH1 = oD1 + SW_TILE_B, oD2 = oH1 + SW_TILE_B;
+  static_assert(sw_lds_bytes(KP0, TWO, true) <= 160 * 1024, "LDS budget");
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, q = lane >> 4;
+  const int nb1 = (p.h1 + 15) >> 4, nb2 = TWO ? (p.h2 + 15) >> 4 : 0;
+  const int nvl = TWO ? p.h2 : p.h1, nbl = TWO ? nb2 : nb1;     // the last hidden layer
+  const int actl = TWO ? p.act2 : p.act1;
+  const float flatl = TWO ? p.flat2 : p.flat1;
+
+  // ---- weights -> LDS, once per block (rows / columns past the real widths are zero)
+  for (int idx = tid; idx < 64 * (KP0 / 8); idx += SM_T) {
+    const int h = idx / (KP0 / 8), c = idx % (KP0 / 8);
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (h < p.h1) v = *(const uint4*)(p.W1 + (size_t)h * KP0 + c * 8);
+    *(uint4*)(smem + oW1 + h * PITCH + ((c ^ (h & 15)) << 4)) = v;
+  }
+  if (TWO)
+    for (int idx = tid; idx < 64 * 64; idx += SM_T) {
+      const int j = idx >> 6, i = idx & 63;
+      ((bf16_t*)(smem + oW2))[idx] = (j < p.h2 && i < p.h1) ? p.W2[(size_t)j * SM_KU + i] : (bf16_t)0;
+    }
+  // the lane's nodes 16 nb + 4 q + i: output weights, layer-2 biases; the output bias
+  float wo[4][4];
+  uint2 b2[4];                     // bf16 as stored, 4 to a register pair
+#pragma unroll
+  for (int nb = 0; nb < 4; ++nb) {
+    unsigned b[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = 16 * nb + 4 * q + i;
+      wo[nb][i] = c < nvl ? p.Wo[c] : 0.f;
+      b[i] = (TWO && c < p.h2) ? (unsigned short)p.W2[(size_t)c * SM_KU + p.h1] : 0u;
+    }
+    b2[nb] = make_uint2(b[0] | b[1] << 16, b[2] | b[3] << 16);
+  }
+  const float bo = p.Wo[nvl];
+  __syncthreads();
+
+  uint4 xf[KS];                    // the wave's 16 rows as MFMA fragments: row lr, k 32 ks + 8 q ..
+  float yn, sn;                    // the loaded tile's target and row weight
+  auto load_x = [&](int tile) __attribute__((always_inline)) {
+    const long row = (long)tile * SW_TILE + 16 * w + lr;
+    const bool ok = row < p.M;
+    const bf16_t* src = p.X + row * p.ldx + 8 * q;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) xf[ks] = ok ? *(const uint4*)(src + 32 * ks) : make_uint4(0, 0, 0, 0);
+    yn = (TRAIN && ok) ? p.Y[row] : 0.f;
+    sn = (TRAIN && ok && p.S) ? p.S[row] : 1.f;
+  };
+
+  f32x4 acc1[4][CB], acc2[4];      // dW1 [h block][column block of the wave's slice], dW2 [j block]
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    acc2[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < CB; ++j) acc1[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  float gwo[4][4], gb2[4][4], gbo = 0.f;   // output-weight / layer-2 bias gradient partials of the lane's row
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) gwo[i][j] = gb2[i][j] = 0.f;
+  double esum = 0.0, wsum = 0.0;
+
+  load_x(blockIdx.x);
+  for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
+    // The swizzled LDS addresses are XORs of lane bits and constants: loop invariants the compiler
+    // would keep in ~60 registers across the tiles, next to dW1's 128 and xf's 64.  The lane index
+    // passes through an empty asm here and before the wgrad, so each phase recomputes its own.
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    const int lr = ln & 15, q = ln >> 4;
+    const float yv = yn, sv = sn;
+    // activation, zero padding, bf16 rounding (where the layer kernels round)
+    auto activate = [&](const f32x4 (&z)[4], uint2 (&pk)[4], int nb_, int nv, int act) __attribute__((always_inline)) {
+      sw_with_act(act, [&](auto A) __attribute__((always_inline)) {
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) {
+          float a[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            a[i] = (nb < nb_ && 16 * nb + 4 * q + i < nv) ? act_fwd(decltype(A)::value, z[nb][i]) : 0.f;
+          pk[nb] = make_uint2(pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]));
+        }
+      });
+    };
+    auto put_tile = [&](int off, const uint2 (&v)[4], int nb_) __attribute__((always_inline)) {
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb)
+        if (nb < nb_) *(uint2*)(smem + off + sm_toff(16 * w + lr, 16 * nb + 4 * q)) = v[nb];
+    };
+
+    // ---- layer 1: Z1^T = W1 X^T (the bias rides in X's 1-column), the X tile goes to LDS
+    f32x4 z1[4];
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb) z1[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      if (TRAIN) *(uint4*)(smem + oX + sm_xoff(16 * w + lr, 32 * ks + 8 * q, PITCH)) = xf[ks];
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb)
+        if (nb < nb1) {
+          const bf16x8 wf = *(const bf16x8*)(smem + oW1 + (16 * nb + lr) * PITCH + (((4 * ks + q) ^ lr) << 4));
+          z1[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, __builtin_bit_cast(bf16x8, xf[ks]), z1[nb], 0, 0, 0);
+        }
+    }
+    load_x(tile + gridDim.x);        // xf is free: the next tile's rows land during the rest of this one
+    uint2 pk1[4], pk2[4];
+    activate(z1, pk1, nb1, p.h1, p.act1);
+    if (TWO) {
+      // ---- layer 2: Z2^T = W2 H1^T + b2; the packed H1 blocks 2 ks, 2 ks + 1 are the B fragment
+      f32x4 z2[4];
+#pragma unroll
+      for (int jb = 0; jb < 4; ++jb) {
+        float b[4];
+        sm_unpk(b2[jb], b);
+        z2[jb] = f32x4{b[0], b[1], b[2], b[3]};
+      }
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+        if (2 * ks < nb1) {
+#pragma unroll
+          for (int jb = 0; jb < 4; ++jb)
+            if (jb < nb2) {
+              const char* wr = smem + oW2 + (16 * jb + lr) * 128 + (32 * ks + 4 * q) * 2;
+              const bf16x8 wf = sm_join(*(const uint2*)wr, *(const uint2*)(wr + 32));
+              z2[jb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, sm_join(pk1[2 * ks], pk1[2 * ks + 1]), z2[jb], 0, 0, 0);
+            }
+        }
+      activate(z2, pk2, nb2, p.h2, p.act2);
+    }
+    const uint2 (&pkl)[4] = TWO ? pk2 : pk1;
+
+    // ---- output neuron, loss, output delta: every lane of a row's 4 holds the same values
+    float zo = 0.f;
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb)
+      if (nb < nbl) {
+        float h[4];
+        sm_unpk(pkl[nb], h);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) zo += h[i] * wo[nb][i];
+      }
+    zo += __shfl_xor(zo, 16, 64);
+    zo += __shfl_xor(zo, 32, 64);
+    zo += bo;
+    const long row = (long)tile * SW_TILE + 16 * w + lr;
+    const bool valid = row < p.M;
+    const float a = act_fwd(p.out_act, zo);
+    if (!TRAIN) {
+      if (valid && q == 0) p.P[row] = a;
+      continue;
+    }
+    float dl, contrib;
+    out_loss_delta(p.out_act, p.loss, true, p.flat_out, zo, a, yv, sv, dl, contrib);
+    if (!valid) dl = 0.f;
+    if (valid && q == 0) { esum += contrib; wsum += sv; }
+    gbo += dl;
+
+    // ---- deltas of the last hidden layer D = dl * Wo * (f'(H) + flat), output-weight gradient
+    uint2 dkl[4];
+    sw_with_act(actl, [&](auto A) __attribute__((always_inline)) {
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb) {
+        float h[4], d[4];
+        sm_unpk(pkl[nb], h);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          d[i] = (nb < nbl && 16 * nb + 4 * q + i < nvl)
+                     ? dl * wo[nb][i] * (act_deriv_out(decltype(A)::value, h[i]) + flatl) : 0.f;
+          gwo[nb][i] += dl * h[i];
+          if (TWO) gb2[nb][i] += d[i];
+        }
+        dkl[nb] = make_uint2(pack_bf16x2(d[0], d[1]), pack_bf16x2(d[2], d[3]));
+      }
+    });
+    if (TWO) {
+      // ---- dgrad: D1^T = (W2^T D2^T) * (f'(H1) + flat1); W2^T fragments by transposed reads
+      f32x4 b1[4];
+#pragma unroll
+      for (int ib = 0; ib < 4; ++ib) b1[ib] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+        if (2 * ks < nb2) {
+#pragma unroll
+          for (int ib = 0; ib < 4; ++ib)
+            if (ib < nb1) {
+              const char* wr = smem + oW2 + (32 * ks + 4 * q + (lr >> 2)) * 128 + (16 * ib + 4 * (ln & 3)) * 2;
+              b1[ib] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sm_tr(wr, wr + 16 * 128),
+                                                               sm_join(dkl[2 * ks], dkl[2 * ks + 1]), b1[ib], 0, 0, 0);
+            }
+        }
+      uint2 dk1[4];
+      sw_with_act(p.act1, [&](auto A) __attribute__((always_inline)) {
+#pragma unroll
+        for (int ib = 0; ib < 4; ++ib) {
+          float h[4], d[4];
+          sm_unpk(pk1[ib], h);
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            d[i] = (ib < nb1 && 16 * ib + 4 * q + i < p.h1)
+                       ? b1[ib][i] * (act_deriv_out(decltype(A)::value, h[i]) + p.flat1) : 0.f;
+          dk1[ib] = make_uint2(pack_bf16x2(d[0], d[1]), pack_bf16x2(d[2], d[3]));
+        }
+      });
+      put_tile(oD1, dk1, nb1);
+      put_tile(oH1, pk1, nb1);
+      put_tile(oD2, dkl, nb2);
+    } else {
+      put_tile(oD1, dkl, nb1);
+    }
+    __syncthreads();
+
+    // ---- wgrad over the tile's 64 rows, 32 per MFMA: dW1 slice [64][KP0 / 4], dW2 slice [64][16]
+    int lw = lane;
+    asm volatile("" : "+v"(lw));
+    const int tp = lw & 3;
+#pragma unroll
+    for (int rs = 0; rs < SW_TILE / 32; ++rs) {
+      const int R = 32 * rs + 8 * (lw >> 4) + ((lw >> 2) & 3);
+      bf16x8 da[4];                  // the D fragments stay, the X fragments stream (4 live registers, not 4 CB)
+#pragma unroll
+      for (int hb = 0; hb < 4; ++hb)
+        if (hb < nb1)
+          da[hb] = sm_tr(smem + oD1 + sm_toff(R, 16 * hb + 4 * tp), smem + oD1 + sm_toff(R + 4, 16 * hb + 4 * tp));
+#pragma unroll
+      for (int cb = 0; cb < CB; ++cb) {
+        const int col = w * (KP0 / 4) + 16 * cb + 4 * tp;
+        const bf16x8 xb = sm_tr(smem + oX + sm_xoff(R, col, PITCH), smem + oX + sm_xoff(R + 4, col, PITCH));
+#pragma unroll
+        for (int hb = 0; hb < 4; ++hb)
+          if (hb < nb1) acc1[hb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da[hb], xb, acc1[hb][cb], 0, 0, 0);
+      }
+      if (TWO && w < nb1) {
+        const bf16x8 hb_ = sm_tr(smem + oH1 + sm_toff(R, 16 * w + 4 * tp), smem + oH1 + sm_toff(R + 4, 16 * w + 4 * tp));
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb)
+          if (jb < nb2) {
+            const bf16x8 da = sm_tr(smem + oD2 + sm_toff(R, 16 * jb + 4 * tp), smem + oD2 + sm_toff(R + 4, 16 * jb + 4 * tp));
+            acc2[jb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da, hb_, acc2[jb], 0, 0, 0);
+          }
+      }
+    }
+    __syncthreads();                 // the tiles are free for the next forward
+  }
+  if (!TRAIN) return;
+
+  // ---- the block's slab row, laid out like the flat parameters: W1 [h1][KP0], (W2 [h2][128],) Wo [128]
+  float* out = p.slab + (size_t)blockIdx.x * p.numel;
+#pragma unroll
+  for (int hb = 0; hb < 4; ++hb)
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int h = 16 * hb + 4 * q + i;
+        if (h < p.h1) out[(size_t)h * KP0 + w * (KP0 / 4) + 16 * cb + lr] = acc1[hb][cb][i];
+      }
+  const long off2 = (long)p.h1 * KP0;
+  if (TWO && 16 * w + lr < p.h1)
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int j = 16 * jb + 4 * q + i;
+        if (j < p.h2) out[off2 + (long)j * SM_KU + 16 * w + lr] = acc2[jb][i];
+      }
+  // per-wave partials through LDS (the X tile is free after the loop's last barrier), summed in
+  // wave order
+  float* sg = (float*)(smem + oX);             // [4][64] output-weight gradient
+  float* sb = sg + 256;                        // [4][64] layer-2 bias gradient
+  float* so = sb + 256;                        // [4] output bias gradient
+  double* se = (double*)(so + 4);              // [4][2] error, weight
+#pragma unroll
+  for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float g = gwo[nb][i], b = gb2[nb][i];
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) { g += __shfl_xor(g, o, 64); b += __shfl_xor(b, o, 64); }
+      if (lr == 0) { sg[w * 64 + 16 * nb + 4 * q + i] = g; sb[w * 64 + 16 * nb + 4 * q + i] = b; }
+    }
+  const float go = wave_sum(q == 0 ? gbo : 0.f);
+  esum = wave_sum_d(esum);
+  wsum = wave_sum_d(wsum);
+  if (lane == 0) { so[w] = go; se[2 * w] = esum; se[2 * w + 1] = wsum; }
+  __syncthreads();
+  if (tid < SM_KU) {
+    float v = 0.f;
+    if (tid < nvl) v = sg[tid] + sg[64 + tid] + sg[128 + tid] + sg[192 + tid];
+    else if (tid == nvl) v = so[0] + so[1] + so[2] + so[3];
+    out[p.numel - SM_KU + tid] = v;
+  }
+  if (TWO) {                                   // W2 columns h1 (bias) .. 127 (padding)
+    const int rest = SM_KU - p.h1;
+    for (int idx = tid; idx < p.h2 * rest; idx += SM_T) {
+      const int j = idx / rest, c = p.h1 + idx % rest;
+      out[off2 + (long)j * SM_KU + c] = c == p.h1 ? sb[j] + sb[64 + j] + sb[128 + j] + sb[192 + j] : 0.f;
+    }
+  }
+  if (tid == 0) {
+    p.err_slab[2 * blockIdx.x] = se[0] + se[2] + se[4] + se[6];
+    p.err_slab[2 * blockIdx.x + 1] = se[1] + se[3] + se[5] + se[7];
+  }
+}
+
 // grad[c] += sum_b slab[b][c], err += sum_b err_slab[b], both in block order
 __global__ __launch_bounds__(256) void small_reduce_kernel(const float* slab, const double* err_slab, int G, long numel,
                                                            float* grad, double* err) {
@@ -406,19 +766,25 @@ __global__ __launch_bounds__(256) void small_reduce_kernel(const float* slab, co
   }
 }
 
-int sm_grid(int M) {
+// rows per block tile of the build that takes kp0
+int sm_tile(int kp0) { return kp0 <= 256 ? SM_TILE : SW_TILE; }
+int sm_tiles(int M, int tile) { return (int)(((long)M + tile - 1) / tile); }
+
+// one block per CU, at most one per tile
+int sm_grid(int M, int tile) {
   int dev = 0, ncu = 256;
   (void)hipGetDevice(&dev);
   (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  const int ntiles = (M + SM_TILE - 1) / SM_TILE;
+  const int ntiles = sm_tiles(M, tile);
   return ntiles < ncu ? ntiles : ncu;
 }
 
 bool sm_act_ok(int a) { return a == 0 || a == 1 || a == 2 || a == 3 || a == 4 || a == 7 || a == 9; }
 
 bool sm_shape_ok(long ldx, int M, int kp0, int h1, int h2, int act1, int act2, int out_act) {
-  return M > 0 && (kp0 == 128 || kp0 == 256) && ldx >= kp0 && ldx % 8 == 0 && h1 >= 1 && h1 <= 64 && h2 >= 0 &&
-         h2 <= 64 && sm_act_ok(act1) && (h2 == 0 || sm_act_ok(act2)) && out_act >= 0 && out_act <= 9;
+  return M > 0 && (kp0 == 128 || kp0 == 256 || kp0 == 384 || kp0 == 512) && ldx >= kp0 && ldx % 8 == 0 && h1 >= 1 &&
+         h1 <= 64 && h2 >= 0 && h2 <= 64 && sm_act_ok(act1) && (h2 == 0 || sm_act_ok(act2)) && out_act >= 0 &&
+         out_act <= 9;
 }
 
 template <int KS, bool TWO, bool TRAIN>
@@ -431,17 +797,30 @@ hipError_t sm_launch(const SmallArgs& p, int grid, hipStream_t stream) {
   return hipGetLastError();
 }
 
+template <int KS, bool TWO, bool TRAIN>
+hipError_t sw_launch(const SmallArgs& p, int grid, hipStream_t stream) {
+  constexpr int lds = sw_lds_bytes(32 * KS, TWO, TRAIN);
+  static const hipError_t attr = hipFuncSetAttribute((const void*)mlp_small_wide_kernel<KS, TWO, TRAIN>,
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  if (attr != hipSuccess) return attr;
+  hipLaunchKernelGGL((mlp_small_wide_kernel<KS, TWO, TRAIN>), dim3(grid), dim3(SM_T), lds, stream, p);
+  return hipGetLastError();
+}
+
 template <bool TRAIN>
 hipError_t sm_dispatch(const SmallArgs& p, int kp0, int grid, hipStream_t stream) {
   if (kp0 == 128) return p.h2 ? sm_launch<4, true, TRAIN>(p, grid, stream) : sm_launch<4, false, TRAIN>(p, grid, stream);
+  if (kp0 == 384) return p.h2 ? sw_launch<12, true, TRAIN>(p, grid, stream) : sw_launch<12, false, TRAIN>(p, grid, stream);
+  if (kp0 == 512) return p.h2 ? sw_launch<16, true, TRAIN>(p, grid, stream) : sw_launch<16, false, TRAIN>(p, grid, stream);
   return p.h2 ? sm_launch<8, true, TRAIN>(p, grid, stream) : sm_launch<8, false, TRAIN>(p, grid, stream);
 }
 
 }  // namespace
 
 // Rows of the slabs shifu_mlp_small_step writes for an M-row chunk (slab [rows][numel] fp32,
-// err_slab [rows][2] fp64): one per block of the persistent grid.
-SHIFU_API int shifu_mlp_small_rows(int M) { return M > 0 ? sm_grid(M) : 0; }
+// err_slab [rows][2] fp64): one per block of the persistent grid.  The 64-row builds have the
+// larger grid, so their count covers every build.
+SHIFU_API int shifu_mlp_small_rows(int M) { return M > 0 ? sm_grid(M, SW_TILE) : 0; }
 
 // Whole gradient step of an M-row chunk of a small MLP: grad [numel] += the chunk's gradient in the
 // flat parameter layout (W1 [h1][kp0], W2 [h2][128] when h2 > 0, Wo [128]), err[2] += (error,
@@ -454,9 +833,9 @@ SHIFU_API int shifu_mlp_small_step(const void* X, long ldx, const void* W1, cons
   if (!sm_shape_ok(ldx, M, kp0, h1, h2, act1, act2, out_act) || (h2 > 0 && W2 == nullptr) || loss < 0 || loss > 5 ||
       numel != (long)h1 * kp0 + (long)h2 * SM_KU + SM_KU)
     return -1;
-  const int grid = sm_grid(M);
+  const int tile = sm_tile(kp0), grid = sm_grid(M, tile);
   SmallArgs p{(const bf16_t*)X, ldx, (const bf16_t*)W1, (const bf16_t*)W2, Wo, Y, S, slab, err_slab, nullptr, numel,
-              M, (M + SM_TILE - 1) / SM_TILE, h1, h2, act1, act2, out_act, loss, flat1, flat2, flat_out};
+              M, sm_tiles(M, tile), h1, h2, act1, act2, out_act, loss, flat1, flat2, flat_out};
   hipError_t e = sm_dispatch<true>(p, kp0, grid, stream);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(small_reduce_kernel, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, stream, slab, err_slab,
@@ -471,7 +850,7 @@ SHIFU_API int shifu_mlp_small_forward(const void* X, long ldx, const void* W1, c
                                       hipStream_t stream) {
   if (!sm_shape_ok(ldx, M, kp0, h1, h2, act1, act2, out_act) || (h2 > 0 && W2 == nullptr) || P == nullptr) return -1;
   SmallArgs p{(const bf16_t*)X, ldx, (const bf16_t*)W1, (const bf16_t*)W2, Wo, nullptr, nullptr, nullptr, nullptr, P, 0,
-              M, (M + SM_TILE - 1) / SM_TILE, h1, h2, act1, act2, out_act, 0, 0.f, 0.f, 0.f};
-  const hipError_t e = sm_dispatch<false>(p, kp0, sm_grid(M), stream);
+              M, sm_tiles(M, sm_tile(kp0)), h1, h2, act1, act2, out_act, 0, 0.f, 0.f, 0.f};
+  const hipError_t e = sm_dispatch<false>(p, kp0, sm_grid(M, sm_tile(kp0)), stream);
   return e == hipSuccess ? 0 : (int)e;
 }

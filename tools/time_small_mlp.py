@@ -1,7 +1,7 @@
 """Time MLPTrainer.step on resident bf16 rows for small nets, fused one-kernel step on and off.
 
     python tools/time_small_mlp.py [--rows 20000000] [--chunk 2097152] [--repeats 3] [--steps 3]
-                                   [--shapes 200-50-1,200-45-45-1,400-64-1] [--arms 0,1]
+                                   [--shapes 200-50-1,...,500-64-64-1] [--arms 0,1]
 
 The arms (SHIFU_MLP_FUSED_SMALL=0 / 1) alternate inside one process on the same rows; every
 repeat is `--steps` whole steps between two device events.  One JSON line per (shape, arm).
@@ -34,7 +34,7 @@ def main():
     ap.add_argument("--chunk", type=int, default=1 << 21)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--shapes", default="200-50-1,200-45-45-1,400-64-1")
+    ap.add_argument("--shapes", default="200-50-1,200-45-45-1,400-64-1,300-50-1,400-45-45-1,500-64-64-1")
     ap.add_argument("--arms", default="0,1")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
